@@ -13,14 +13,19 @@ next chunk is coded (double-buffered staging on the device, a copy stream).
 With N > 1 the reads are sharded in file order (total work fixed: "scaling": "strong"), the k-mer set, the reference reads and
 the index are replicated through the two exchanges of SURVEY.md §8e (RCCL via torch.distributed), and the compressed parts
 are gathered to rank 0 inside the step.  Not in the step: FASTQ parsing, the header (ID) stream, the archive container.
-After the timed steps the output is checked: the first `dna` parts of the last pass are decoded by the library's host decoder
-(cl_dna_decode_part) and compared with the generator's bases (`round_trip_checked`).
 
-Also in the JSON line: `archive_vs_ref` — on a bounded sample of the same recipe, written as FASTQ by the host form of the
-generator (bit-identical to the device form), the archive of `colord_amd/colord_hip` (same library, reference part cut)
-divided by the archive of the unmodified reference (`oracle/_ref/colord`), which is also the timed `cpu_baseline`.
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given, and prints the line
+(headline, per-kernel HIP-event times of the timed steps).  Everything else runs only with --full:
+  * every timed pass is digested part by part between the timing brackets (`parts_digest_stable`);
+  * the first `dna` / `qual` parts of the last pass are decoded by the library's host decoders and compared with the generator's
+    bases and quantised qualities (`round_trip_checked`);
+  * one more pass with the reference's coder parts (`ref_cut`);
+  * `archive_vs_ref` — on a bounded sample of the same recipe, written as FASTQ by the host form of the generator (bit-identical to
+    the device form), the archive of `colord_amd/colord_hip` (same library, reference part cut) divided by the archive of the
+    unmodified reference (`oracle/_ref/colord`), which is also the timed `cpu_baseline`;
+  * the command-line compressor file to archive (`t_e2e`), and at N > 1 the RCCL self-test before the passes.
 
-Contract: python bench.py --gpus N --steps K --warmup W   (N>1 via torch.distributed.run, one rank/GPU).
+Contract: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]   (N>1 via torch.distributed.run, one rank/GPU).
 Rank 0 prints ONE JSON line.
 """
 from __future__ import annotations
@@ -64,15 +69,26 @@ def parse():
                     help="part (= range-coder restart) size in symbols.  4194304 reproduces the reference's packs (defs.h:45) and its exact "
                          "bytes; smaller parts are equally valid archives (the reference decoder follows the part table), cost 8 flush "
                          "bytes each (+0.04 %% at 64 Ki) and expose the parallelism the per-part dependent chain needs")
-    ap.add_argument("--deadline-s", type=float, default=1500.0,
-                    help="wall-clock budget of the whole process (the driver stops a run after 1800 s).  If (steps + warmup) passes over --bases "
+    ap.add_argument("--deadline-s", type=float, default=None,
+                    help="wall-clock budget of the whole process (default 1500 s, 540 s with --full).  If (steps + warmup) passes over --bases "
                          "cannot finish inside it — estimated up front at 1.1 Gbases/s/GPU, then checked against the first warm-up pass — the input "
                          "is cut to a prefix of the file that can, and `config.workload` says so")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and side measurements: per-pass digests, round trip through the host decoders, the pass with the "
+                         "reference's part cut, CPU baseline and archive-size check, command-line compressor (T_e2e), RCCL self-test at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (N = 1 only): the part sizes of the "
+                         "`dna` and `qual` streams (float64, every part) and a fixed, seeded sample of their bytes (float32)")
     ap.add_argument("--e2e-bases", type=float, default=2.0e10, help="bases of the FASTQ the command-line compressor is timed on, file to archive (T_e2e); 0: skip")
     ap.add_argument("--no-qual", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ref-cut", action="store_true", help="skip the extra pass with the reference's 4-Mi-symbol coder parts (the byte-identical mode)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.deadline_s is None:
+        args.deadline_s = 540.0 if args.full else 1500.0
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
+    return args
 
 
 # ONT default ("memory") preset: arg_parse.cpp:89-408 / SURVEY App. B
@@ -660,6 +676,23 @@ def load_traffic(kernel: str):
     return e["hbm_bytes_per_launch"], t.get("source")
 
 
+DUMP_SAMPLE_BYTES = 1 << 22          # per stream: 16 MB as float32; with the part sizes (~6 MB per stream at 50 Gbases) well under 64 MB
+
+
+def dump_outputs(out_dir: str, sink: HostSink):
+    """What the last timed pass handed its caller, as .npy files: per stream (`dna`, `qual`) the size of every part, in order
+    (float64, exact), and the bytes at DUMP_SAMPLE_BYTES positions drawn with a fixed seed over the stream's length (float32, exact).
+    The input is fixed by the arguments, so two builds run with the same arguments can be compared file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, h, sizes, n in (("dna", sink.h_dna, sink.dna_sizes, sink.do), ("qual", sink.h_qual, sink.qual_sizes, sink.qo)):
+        if h is None:
+            continue
+        sz = np.concatenate(sizes) if sizes else np.zeros(0, np.uint64)
+        np.save(os.path.join(out_dir, f"{name}_part_sizes.npy"), sz.astype(np.float64))
+        pos = np.sort(np.random.default_rng(20240917).integers(0, max(n, 1), size=min(n, DUMP_SAMPLE_BYTES)))
+        np.save(os.path.join(out_dir, f"{name}_bytes_sample.npy"), h.numpy()[pos].astype(np.float32))
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -680,7 +713,7 @@ def main():
             cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1", "--master-port", str(port),
                    os.path.abspath(__file__)] + sys.argv[1:]
             sys.stdout.flush(); sys.stderr.flush()
-            os.execvpe(cmd[0], cmd, env)
+            sys.exit(subprocess.call(cmd, env=env))          # (a child process: this one may have initialised the GPU runtime)
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}", file=sys.stderr)
         sys.exit(2)
     backend = os.environ.get("BENCH_BACKEND", "nccl")      # "gloo": functional check of the multi-rank path with ranks sharing GPUs
@@ -697,7 +730,7 @@ def main():
     from colord_amd import ontsim, parallel as par
 
     preflight = None
-    if world > 1:
+    if world > 1 and args.full:
         # N > 1 preflight, before any context exists: the C++ host's RCCL collectives alone (`colord_hip rccl-selftest`: all-gather, all-to-all-v
         # and all-gather-v with uneven and empty shares, every byte checked) on as many GPUs as the box has for the ranks — a broken fabric or a
         # broken RCCL shows here in seconds, with its message in the line, instead of as a hang of the 50-Gbase passes
@@ -715,7 +748,7 @@ def main():
 
     # N = 1: the command-line leg (T_e2e) FIRST, while this process has not touched the GPU (see `t_e2e.what`)
     e2e_first = None
-    if world == 1 and args.e2e_bases > 0 and not args.no_cpu_baseline:
+    if world == 1 and args.full and args.e2e_bases > 0 and not args.no_cpu_baseline:
         k_, a_ = kmer_anchor_len(float(args.bases))
         k_, a_ = (args.k or k_), (args.a or a_)
         try:
@@ -726,7 +759,7 @@ def main():
     qctx = Context(local, timing=not os.environ.get("BENCH_NO_TIMING")) if not os.environ.get("BENCH_NO_OVERLAP") else None
     bases = float(args.bases)
     # what the passes may take: the deadline minus what is spent already, the CPU-baseline / size-check leg (~1.5 min) and a margin
-    reserve_s = (100.0 if (world == 1 and not args.no_cpu_baseline) else 30.0) + 30.0
+    reserve_s = (100.0 if (world == 1 and args.full and not args.no_cpu_baseline) else 30.0) + 30.0
     pass_budget_s = max(10.0, args.deadline_s - (time.time() - T_PROCESS_START) - reserve_s - bases / 5e9)
     est_s = (args.steps + args.warmup) * bases / (2.0e9 * world)             # (25 s a pass of 50 Gbases on one GPU: measured 17-18)
     reduced = False
@@ -786,8 +819,8 @@ def main():
     ctx.acc.clear()
     if qctx is not None:
         qctx.acc.clear()
-    # K steps, each bracketed by barrier + synchronize on both sides; between two brackets (never inside one) the pass that just
-    # ended is digested part by part where the step left it: `parts_digest_stable` = every timed pass gave the same bytes
+    # K steps, each bracketed by barrier + synchronize on both sides; with --full, between two brackets (never inside one) the pass that
+    # just ended is digested part by part where the step left it: `parts_digest_stable` = every timed pass gave the same bytes
     info, dt, step_s, own_s, digests = None, 0.0, [], [], []
     for _ in range(args.steps):
         sync()
@@ -798,8 +831,10 @@ def main():
         sync()
         step_s.append(time.perf_counter() - t0)
         dt += step_s[-1]
-        if not os.environ.get("BENCH_NO_DIGEST"):
+        if args.full and not os.environ.get("BENCH_NO_DIGEST"):
             digests.append(pass_digest(sink, dna_out, qual_out, info))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sink)                # (before anything else writes to the sink)
     digest_stable = bool(digests) and all(d == digests[0] for d in digests)
     digest_diff = ""
     for i, d in enumerate(digests):
@@ -885,7 +920,7 @@ def main():
         # one dependent chain of the interval coder, 64 times longer than with the bench's default cut) — when the deadline allows
         ref_cut = None
         rt = None
-        if world == 1 and not args.no_ref_cut and args.pack_symbols != (1 << 22):
+        if world == 1 and args.full and not args.no_ref_cut and args.pack_symbols != (1 << 22):
             left = args.deadline_s - (time.time() - T_PROCESS_START) - reserve_s
             if left > 4.0 * (dt / args.steps):
                 torch.cuda.synchronize()
@@ -903,12 +938,12 @@ def main():
                            "dna_bytes": inf2["dna_bytes"], "qual_bytes": inf2["qual_bytes"], "parts": sum(len(c[2]) - 1 for c in shard.chunks),
                            "stream_bytes_vs_default_cut": (inf2["dna_bytes"] + inf2["qual_bytes"]) / max(1, total_dna + total_qual),
                            "note": "same input, one pass, coder parts = the reference's reader packs: the streams are the reference's bytes (size_check.streams_vs_ref_ref_cut)"}
-        if rt is None and sink is not None:
+        if args.full and rt is None and sink is not None:
             rt = round_trip_check(ctx, table, shard, sink, prm, info, r0, qa=QA if not args.no_qual else None)
         timer_txt = ("T_core (SURVEY 8d): packed bases + quality bytes resident in HBM -> every compressed part in pinned host memory" if sink is not None
                      else "packed bases + quality bytes resident in HBM -> every compressed part gathered to rank 0 (device)")
         cb, size, e2e = (None, None, None)
-        if world > 1 and args.e2e_bases > 0 and not args.no_cpu_baseline:
+        if world > 1 and args.full and args.e2e_bases > 0 and not args.no_cpu_baseline:
             # N > 1, second leg: the PRODUCT's multi-GPU host (`colord_hip --gpus N`: C++, one rank thread per GPU, RCCL) file -> archive on
             # the same GPUs.  Every rank gives its memory back first (the ranks of this process group stay alive, idle, until the leg is through).
             shard.free()
@@ -924,7 +959,7 @@ def main():
                 e2e = {"error": repr(e)[:400]}
             ctx = Context(local)
             qctx = Context(local) if qctx is not None else None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             shard.free()                                    # the sample runs (and the command-line compressor) need the memory:
             del dna_out, qual_out, sink                     # give everything back, pools included, and start from fresh contexts
             ctx.close()
@@ -972,6 +1007,11 @@ def main():
                        "input_generation_s": round(t_gen, 1), "rank0_sizes": info},
             "roofline": roof, "cpu_baseline": cb, "size_check": size, "ref_cut": ref_cut, "t_e2e": e2e,
         }
+        if not args.full:                                   # (what only --full measures or checks is left out, not reported as failed)
+            for k_ in ("archive_vs_ref", "round_trip_checked", "qual_round_trip_checked", "round_trip", "parts_digest_stable", "parts_digest",
+                       "bench_parts_sha256_equal_ref", "cpu_baseline", "size_check", "ref_cut", "t_e2e"):
+                del line[k_]
+            line["step_s"] = [round(x, 3) for x in step_s]
         if multi is not None:
             # one model domain per rank is the only place sharding changes bytes: stream bytes per base here over the committed one-GPU run's
             one = None
@@ -991,7 +1031,7 @@ def main():
         print(json.dumps(line))
     else:
         shard.free()
-        if world > 1 and args.e2e_bases > 0 and not args.no_cpu_baseline:
+        if world > 1 and args.full and args.e2e_bases > 0 and not args.no_cpu_baseline:
             del dna_out, qual_out
             ctx.close()
             if qctx is not None:

@@ -274,7 +274,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` from a plain python command (the shape of the driver's N = 1 command): bench.py starts its ranks itself —
     here two ranks sharing this box's GPU over gloo — and rank 0 prints the one JSON line with n_gpus = 2."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", BENCH_BACKEND="gloo", PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--bases", "2e8", "--chunk-bases", "5e7", "--e2e-bases", "1e8"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "1", "--warmup", "0", "--bases", "2e8", "--chunk-bases", "5e7", "--e2e-bases", "1e8"],
                        capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

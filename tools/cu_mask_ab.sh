@@ -1,12 +1,12 @@
 #!/bin/bash
 # A/B of CU partitioning at 50 Gbases: one warm pass + one timed pass of the default bench per setting of COLORD_HIP_CU_MASK;
 # prints the pass time and k_range_code's / k_dna_walk's / k_lis_anchors' time per launch.  Run through gpurun from the repo root.
-R=$GRAFT_REPO_ROOT; cd $R; mkdir -p gpurun_out/cu_mask
+cd "$(dirname "$0")/.."; D=ab_out/cu_mask; mkdir -p $D
 i=0
 for M in "" "$@"; do
   i=$((i+1))
-  COLORD_HIP_CU_MASK="$M" python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-ref-cut --e2e-bases 0 > gpurun_out/cu_mask/run_$i.json 2> gpurun_out/cu_mask/run_$i.err
-  python - "$M" gpurun_out/cu_mask/run_$i.json <<'PY'
+  COLORD_HIP_CU_MASK="$M" python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-ref-cut --e2e-bases 0 > $D/run_$i.json 2> $D/run_$i.err
+  python - "$M" $D/run_$i.json <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

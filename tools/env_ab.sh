@@ -1,11 +1,11 @@
 #!/bin/bash
 # A/B of environment settings at 50 Gbases: one warm + one timed pass of the default bench per argument ("VAR=value VAR2=value ..."; "" = defaults).
-R=$GRAFT_REPO_ROOT; cd $R; mkdir -p gpurun_out/env_ab
+cd "$(dirname "$0")/.."; D=ab_out/env_ab; mkdir -p $D
 i=0
 for M in "$@"; do
   i=$((i+1))
-  env $M python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-ref-cut --e2e-bases 0 $BENCH_EXTRA > gpurun_out/env_ab/run_$i.json 2> gpurun_out/env_ab/run_$i.err
-  python - "$M" gpurun_out/env_ab/run_$i.json <<'PY'
+  env $M python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-ref-cut --e2e-bases 0 $BENCH_EXTRA > $D/run_$i.json 2> $D/run_$i.err
+  python - "$M" $D/run_$i.json <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
