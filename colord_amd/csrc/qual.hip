@@ -34,8 +34,24 @@ struct QualCfg {
 	uint32_t max_total, adder;
 	uint32_t n_ctx;                                // dense context count of the per-base family
 	uint32_t is_avg, is_thr;
+	uint32_t hist_radix, n_hist;                   // values a history field takes, and histories: hist_radix ^ n_ctx_sym (qual_hist_radix)
+	uint32_t dense_bits;                           // bits of a context id: ids are 0 .. n_ctx - 1 <= 2^dense_bits
 	uint8_t map_fwd[96], quant[96];
 };
+
+// ---- context ids ------------------------------------------------------------------------------------
+// The id of a context is private to this file: the sort only has to bring equal contexts together in stream order, and the models start
+// uniform (k_init_state), so any one-to-one numbering gives the same triples.  Ids are therefore DENSE: a history field holds a symbol
+// 0 .. n_sym - 1 or "no such position" (= n_sym), the n_ctx_sym fields are packed in base n_sym + 1, and the base context (and the
+// edit-script flags of levels 2 and 3) multiply on top.  4-avg / 4-thr: 125 histories x 256 = 32 000 ids, 15 bits (bit fields: 17);
+// 5-*: 216 x 256, 16 bits (17); 2-*: 729 x 256, 18 bits (20).  QM_ORIGINAL keeps its bit fields: the quantised values fill them.
+__host__ __device__ inline uint32_t qual_hist_radix(const QualCfg& c) { return c.mode == QM_ORIGINAL ? 1u << c.bits_per_sym : c.n_sym + 1; }
+// history so far + the field of the position t + 1 back, whose place value is `place` (1, radix, radix^2 ...)
+__host__ __device__ inline uint32_t qual_hist_add(uint32_t hist, uint32_t place, uint32_t field) { return hist + place * field; }
+__host__ __device__ inline uint32_t qual_ctx_id(const QualCfg& c, uint32_t hist, uint32_t bctx, uint32_t fl)
+{
+	return hist + c.n_hist * (bctx | (fl << c.base_bits));
+}
 
 } // namespace
 
@@ -47,7 +63,7 @@ struct QualGroupPrep {
 	uint32_t p0 = 0, p1 = 0, np = 0, ng = 0; uint64_t n_base = 0, n_syms = 0, n_byte = 0, trip_words = 0;
 	std::vector<uint32_t> rank, plen_r;
 	DevBuf<uint64_t> d_gbase; DevBuf<uint32_t> d_plen;
-	DevBuf<uint32_t> key, sidx, bkey, bsidx, ss, se, bss, bse;
+	DevBuf<uint32_t> key, sidx, bkey, bsidx, bss, bse;
 };
 struct QualPrepared {
 	const cl_reads* R = nullptr; const uint8_t* d_quals = nullptr; std::vector<uint32_t> part_bounds;
@@ -153,24 +169,24 @@ __global__ __launch_bounds__(256) void k_qual_symbols(const QualCfg* __restrict_
 	}
 	if (cfg.mode == QM_AVERAGE || cfg.mode == QM_NONE) { if (__ballot(out_of_range) && lane == 0) atomicOr(bad, 1u); return; }
 
-	const uint32_t sym_mask = (1u << cfg.bits_per_sym) - 1;
+	const uint32_t radix = cfg.hist_radix, missing = radix - 1;
 	for (uint32_t i = lane; i < len; i += 64)
 	{
 		uint32_t qv = quals[qb + i] - 33u;
 		if (qv > 95u) { out_of_range = true; qv = 0; }
 		uint32_t sym = cfg.map_fwd[qv];
-		// history: context values of positions i-1 .. i-n (missing = all ones)
-		uint32_t hist = 0;
-		for (uint32_t t = 1; t <= cfg.n_ctx_sym; ++t)
+		// history: context values of positions i-1 .. i-n (missing = the field's last value), packed in base `radix`
+		uint32_t hist = 0, place = 1;
+		for (uint32_t t = 1; t <= cfg.n_ctx_sym; ++t, place *= radix)
 		{
-			uint32_t v = sym_mask;
+			uint32_t v = missing;
 			if (i >= t)
 			{
 				const uint32_t qp = quals[qb + i - t] - 33u;                          // (checked at its own position)
 				uint32_t s = cfg.map_fwd[qp > 95u ? 0u : qp];
-				v = cfg.mode == QM_ORIGINAL ? cfg.quant[s] : s;
+				v = cfg.mode == QM_ORIGINAL ? (cfg.quant[s] & missing) : s;
 			}
-			hist |= (v & sym_mask) << ((t - 1) * cfg.bits_per_sym);
+			hist = qual_hist_add(hist, place, v);
 		}
 		uint32_t b0 = arena_base(packed, wb, i);
 		uint32_t bm1 = i > 0 ? arena_base(packed, wb, i - 1) : 0;
@@ -183,14 +199,13 @@ __global__ __launch_bounds__(256) void k_qual_symbols(const QualCfg* __restrict_
 		else bctx = b0 | (bm1 << 2) | ((uint32_t)(i > 1 && bm2 == bm1) << 4) | (bp1 << 5);
 		uint32_t fl = 0;
 		if (cfg.level > 1 && flags) { uint8_t c = flags[qb + i]; fl = (c == 'M' ? 1u : 0u) | (c == 'A' ? 2u : 0u); }
-		uint32_t ctx = hist | (bctx << cfg.ctx_bits) | (fl << (cfg.ctx_bits + cfg.base_bits));
-		key[k_read + i] = (ctx << cfg.sym_bits) | sym;
+		key[k_read + i] = (qual_ctx_id(cfg, hist, bctx, fl) << cfg.sym_bits) | sym;
 		sidx_out[k_read + i] = trip_index(lay, part, s_read + navg + i);
 	}
 	if (__ballot(out_of_range) && lane == 0) atomicOr(bad, 1u);
 }
 
-// ---- Q3: run bounds of every context in the sorted key array --------------------------------------
+// ---- Q3: run bounds of every context in the sorted key array (byte family: a few symbols per read) ----
 __global__ void k_seg_bounds(const uint32_t* __restrict__ skey, uint64_t n, uint32_t shift, uint32_t* __restrict__ seg_start, uint32_t* __restrict__ seg_end)
 {
 	uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -200,20 +215,39 @@ __global__ void k_seg_bounds(const uint32_t* __restrict__ skey, uint64_t n, uint
 	if (j + 1 == n || (skey[j + 1] >> shift) != c) seg_end[c] = (uint32_t)j + 1;
 }
 
+// First index in [lo, n) whose context (key >> shift) is >= c, n if there is none, in keys sorted by context: a 64-ary search by one wave,
+// one load per lane and round, <= 6 rounds for 2^32 keys.  The per-base family finds its context runs with it (two searches per wave)
+// instead of a pass over all keys that writes every run's bounds.
+__device__ inline uint32_t wave_ctx_lower_bound(const uint32_t* __restrict__ skey, uint32_t lo, uint32_t n, uint32_t shift, uint32_t c, uint32_t lane)
+{
+	uint32_t hi = n;                                                              // the answer is in [lo, hi]
+	while (hi > lo)
+	{
+		const uint32_t step = (hi - lo) / 64 + 1;                                 // probes at lo + (lane + 1) * step - 1; lane 63's is >= hi
+		const uint64_t p = (uint64_t)lo + (uint64_t)(lane + 1) * step - 1;
+		const bool ge = p < hi ? (skey[p] >> shift) >= c : true;
+		const uint32_t f = (uint32_t)__builtin_ctzll(__ballot(ge));               // first probe at or behind the answer (monotone: never empty)
+		const uint64_t nhi = (uint64_t)lo + (uint64_t)(f + 1) * step - 1;
+		lo += f * step;
+		if (nhi < hi) hi = (uint32_t)nhi;
+	}
+	return lo;
+}
+
 // ---- Q4a: model evolution for alphabets of <= 5 symbols: one wave per context ----------------------
 // 64 symbols per step: per-class ballots give every lane the number of earlier same-class symbols of the
 // step; the rescale instant follows from the total alone.
 template<uint32_t A>
-__global__ __launch_bounds__(256) void k_evolve_small(const uint32_t* __restrict__ skey, const uint32_t* __restrict__ sval,
-                                                     const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ seg_end,
+__global__ __launch_bounds__(256) void k_evolve_small(const uint32_t* __restrict__ skey, const uint32_t* __restrict__ sval, uint32_t n,
                                                      uint32_t n_ctx, uint32_t sym_bits, uint32_t max_total, uint32_t adder,
                                                      uint32_t* __restrict__ state, triple_t* __restrict__ trip)
 {
 	const uint32_t c = blockIdx.x * 4 + (threadIdx.x >> 6);
 	if (c >= n_ctx) return;
-	const uint32_t s = seg_start[c], e = seg_end[c];
-	if (e <= s) return;
 	const uint32_t lane = threadIdx.x & 63;
+	const uint32_t s = wave_ctx_lower_bound(skey, 0, n, sym_bits, c, lane);       // the run of context c in the sorted keys
+	if (s >= n || (skey[s] >> sym_bits) != c) return;
+	const uint32_t e = wave_ctx_lower_bound(skey, s + 1, n, sym_bits, c + 1, lane);
 	const uint64_t lt = (1ULL << lane) - 1;
 	uint32_t st[A]; uint32_t tot;
 #pragma unroll
@@ -278,7 +312,7 @@ __global__ __launch_bounds__(256) void k_evolve_small(const uint32_t* __restrict
 // their exclusive prefix in LDS, 64 symbols per step.  Inside a step lane l needs, besides the table
 // values, the number of earlier lanes of the step with a smaller / an equal symbol (uniform readlane loop).
 __global__ __launch_bounds__(256) void k_evolve_large(const uint32_t* __restrict__ skey, const uint32_t* __restrict__ sval,
-                                                     const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ seg_end,
+                                                     const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ seg_end, uint32_t n,
                                                      uint32_t n_ctx, uint32_t n_sym, uint32_t sym_bits, uint32_t max_total, uint32_t adder,
                                                      uint32_t* __restrict__ state, triple_t* __restrict__ trip)
 {
@@ -287,9 +321,15 @@ __global__ __launch_bounds__(256) void k_evolve_large(const uint32_t* __restrict
 	const uint32_t w = threadIdx.x >> 6;
 	const uint32_t c = blockIdx.x * 4 + w;
 	if (c >= n_ctx) return;
-	const uint32_t s = seg_start[c], e = seg_end[c];
-	if (e <= s) return;
 	const uint32_t lane = threadIdx.x & 63;
+	uint32_t s, e;
+	if (seg_start) { s = seg_start[c]; e = seg_end[c]; }                           // byte family: bounds from k_seg_bounds
+	else
+	{	// per-base family: the run of context c by search in the n sorted keys (as k_evolve_small)
+		s = wave_ctx_lower_bound(skey, 0, n, sym_bits, c, lane);
+		e = s < n && (skey[s] >> sym_bits) == c ? wave_ctx_lower_bound(skey, s + 1, n, sym_bits, c + 1, lane) : s;
+	}
+	if (e <= s) return;
 	uint32_t* sp = state + (uint64_t)c * (n_sym + 1);
 	uint32_t* cnt = s_cnt[w]; uint32_t* pre = s_pre[w];
 #pragma unroll
@@ -418,9 +458,15 @@ extern "C" cl_status cl_qual_coder_create(cl_ctx* ctx, const cl_qual_params* prm
 	}
 	c.ctx_bits = c.bits_per_sym * c.n_ctx_sym;
 	c.sym_bits = 1; while ((1u << c.sym_bits) < c.n_sym) ++c.sym_bits;
-	uint32_t total_ctx_bits = c.ctx_bits + c.base_bits + (c.level > 1 ? 2 : 0);
-	if (total_ctx_bits + c.sym_bits > 32) return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_qual_coder_create: context does not fit 32-bit keys");
-	c.n_ctx = (c.mode == QM_AVERAGE || c.mode == QM_NONE) ? 1u : (1u << total_ctx_bits);
+	// dense context ids (qual_ctx_id): the count is one more than the id of the last history with every other field at its largest value
+	c.hist_radix = qual_hist_radix(c); c.n_hist = 1;
+	for (uint32_t t = 0; t < c.n_ctx_sym; ++t) c.n_hist *= c.hist_radix;
+	const uint64_t n_ctx64 = (uint64_t)c.n_hist << (c.base_bits + (c.level > 1 ? 2 : 0));
+	if (n_ctx64 > (1ull << 30)) return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_qual_coder_create: context does not fit 32-bit keys");
+	c.n_ctx = (c.mode == QM_AVERAGE || c.mode == QM_NONE) ? 1u : (uint32_t)n_ctx64;
+	c.dense_bits = 0; while ((1ull << c.dense_bits) < c.n_ctx) ++c.dense_bits;
+	if (c.dense_bits + c.sym_bits > 32 || (c.n_ctx > 1 && qual_ctx_id(c, c.n_hist - 1, (1u << c.base_bits) - 1, c.level > 1 ? 3u : 0u) != c.n_ctx - 1))
+		return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_qual_coder_create: context ids do not fit the bits the sort is asked for");
 	DEV_ALLOC(ctx, Q->d_cfg, 1);
 	HIP_TRY(ctx, hipMemcpyAsync(Q->d_cfg.p, &c, sizeof(c), hipMemcpyHostToDevice, ctx->stream));
 	DEV_ALLOC(ctx, Q->state, (uint64_t)c.n_ctx * (c.n_sym + 1));
@@ -520,16 +566,8 @@ cl_status qual_prepare(cl_ctx* ctx, cl_qual_coder* Q, const cl_reads* R, const u
 			LAUNCHB(ctx, n_base * (1.0 + 0.25 + 8.0) + n_byte * 8.0, k_qual_symbols, grid_for(r1 - r0, 4), 256, (const QualCfg*)Q->d_cfg.p, (const uint64_t*)R->packed.p, (const uint64_t*)R->word_off.p,
 				d_quals, d_qual_off, d_flags, r0, r1, qo[p0], lay, key.p, sidx.p, bkey.p, bsidx.p, bad.p);
 		HIP_TRY(ctx, hipGetLastError());
-		const uint32_t total_ctx_bits = c.ctx_bits + c.base_bits + (c.level > 1 ? 2 : 0);
-		if (per_base && n_base)
-		{
-			CL_TRY(dev_sort_keys32_pairs(ctx, key.p, sidx.p, n_base, c.sym_bits, c.sym_bits + total_ctx_bits));
-			DEV_ALLOC(ctx, G.ss, c.n_ctx); DEV_ALLOC(ctx, G.se, c.n_ctx);
-			HIP_TRY(ctx, hipMemsetAsync(G.ss.p, 0, (uint64_t)c.n_ctx * 4, ctx->stream));
-			HIP_TRY(ctx, hipMemsetAsync(G.se.p, 0, (uint64_t)c.n_ctx * 4, ctx->stream));
-			LAUNCH(ctx, k_seg_bounds, grid_for(n_base, 256), 256, (const uint32_t*)key.p, n_base, c.sym_bits, G.ss.p, G.se.p);
-			HIP_TRY(ctx, hipGetLastError());
-		}
+		// (the dense ids of the default mode are 15 bits: two 8-bit passes.  The context runs are found by the model kernels themselves.)
+		if (per_base && n_base) CL_TRY(dev_sort_keys32_pairs(ctx, key.p, sidx.p, n_base, c.sym_bits, c.sym_bits + c.dense_bits));
 		if (n_byte)
 		{
 			CL_TRY(dev_sort_keys32_pairs(ctx, bkey.p, bsidx.p, n_byte, 8, 8 + 10));
@@ -590,16 +628,16 @@ cl_status qual_evolve_batch(cl_ctx* ctx, cl_qual_coder* Q, const cl_reads* R, co
 			const uint32_t g = grid_for(c.n_ctx, 4);
 			switch (c.n_sym)
 			{
-			case 2: LAUNCHB(ctx, n_base * 16.0, (k_evolve_small<2>), g, 256, (const uint32_t*)G.key.p, (const uint32_t*)G.sidx.p, (const uint32_t*)G.ss.p, (const uint32_t*)G.se.p, c.n_ctx, c.sym_bits, c.max_total, c.adder, Q->state.p, trip.p); break;
-			case 4: LAUNCHB(ctx, n_base * 16.0, (k_evolve_small<4>), g, 256, (const uint32_t*)G.key.p, (const uint32_t*)G.sidx.p, (const uint32_t*)G.ss.p, (const uint32_t*)G.se.p, c.n_ctx, c.sym_bits, c.max_total, c.adder, Q->state.p, trip.p); break;
-			case 5: LAUNCHB(ctx, n_base * 16.0, (k_evolve_small<5>), g, 256, (const uint32_t*)G.key.p, (const uint32_t*)G.sidx.p, (const uint32_t*)G.ss.p, (const uint32_t*)G.se.p, c.n_ctx, c.sym_bits, c.max_total, c.adder, Q->state.p, trip.p); break;
-			default: LAUNCHB(ctx, n_base * 16.0, k_evolve_large, g, 256, (const uint32_t*)G.key.p, (const uint32_t*)G.sidx.p, (const uint32_t*)G.ss.p, (const uint32_t*)G.se.p, c.n_ctx, c.n_sym, c.sym_bits, c.max_total, c.adder, Q->state.p, trip.p); break;
+			case 2: LAUNCHB(ctx, n_base * 16.0, (k_evolve_small<2>), g, 256, (const uint32_t*)G.key.p, (const uint32_t*)G.sidx.p, (uint32_t)n_base, c.n_ctx, c.sym_bits, c.max_total, c.adder, Q->state.p, trip.p); break;
+			case 4: LAUNCHB(ctx, n_base * 16.0, (k_evolve_small<4>), g, 256, (const uint32_t*)G.key.p, (const uint32_t*)G.sidx.p, (uint32_t)n_base, c.n_ctx, c.sym_bits, c.max_total, c.adder, Q->state.p, trip.p); break;
+			case 5: LAUNCHB(ctx, n_base * 16.0, (k_evolve_small<5>), g, 256, (const uint32_t*)G.key.p, (const uint32_t*)G.sidx.p, (uint32_t)n_base, c.n_ctx, c.sym_bits, c.max_total, c.adder, Q->state.p, trip.p); break;
+			default: LAUNCHB(ctx, n_base * 16.0, k_evolve_large, g, 256, (const uint32_t*)G.key.p, (const uint32_t*)G.sidx.p, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t)n_base, c.n_ctx, c.n_sym, c.sym_bits, c.max_total, c.adder, Q->state.p, trip.p); break;
 			}
 			HIP_TRY(ctx, hipGetLastError());
 		}
 		if (n_byte)
 		{
-			LAUNCH(ctx, k_evolve_large, grid_for(BYTE_CTX, 4), 256, (const uint32_t*)G.bkey.p, (const uint32_t*)G.bsidx.p, (const uint32_t*)G.bss.p, (const uint32_t*)G.bse.p,
+			LAUNCH(ctx, k_evolve_large, grid_for(BYTE_CTX, 4), 256, (const uint32_t*)G.bkey.p, (const uint32_t*)G.bsidx.p, (const uint32_t*)G.bss.p, (const uint32_t*)G.bse.p, (uint32_t)n_byte,
 				BYTE_CTX, 256u, 8u, 1u << 18, 8u, Q->bstate.p, trip.p);
 			HIP_TRY(ctx, hipGetLastError());
 		}

@@ -18,7 +18,7 @@ constexpr uint32_t STILE = ST * SI;     // 4096 keys per tile
 // per block wrote every count into a sector of its own: 275 MB of counts cost 1.7 GB of HBM writes per pass of the DNA coder's sort by the
 // round's first WRITE_SIZE pass; 0.39 -> 0.09 GB per launch on average since, profiles/r05_pmc_traffic_summary.txt.)  G = 1 for the small sorts, whose few tiles are wanted on as many CUs as there are tiles.
 template<typename K, uint32_t DB, uint32_t G>
-__global__ __launch_bounds__(ST) void k_sort_hist(const K* __restrict__ keys, uint64_t n, uint32_t shift,
+__global__ __launch_bounds__(ST) void k_sort_hist(const K* __restrict__ keys, uint64_t n, uint32_t shift, uint32_t dmask,
                                                   uint32_t* __restrict__ hist, uint32_t nb)
 {
 	constexpr uint32_t ND = 1u << DB;
@@ -34,7 +34,7 @@ __global__ __launch_bounds__(ST) void k_sort_hist(const K* __restrict__ keys, ui
 		for (uint32_t i = 0; i < SI; ++i)
 		{
 			uint64_t idx = base + (uint64_t)i * ST + threadIdx.x;
-			if (idx < n) atomicAdd(&h[g * ROW + ((uint32_t)(keys[idx] >> shift) & (ND - 1))], 1u);
+			if (idx < n) atomicAdd(&h[g * ROW + ((uint32_t)(keys[idx] >> shift) & dmask)], 1u);
 		}
 	}
 	__syncthreads();
@@ -48,8 +48,10 @@ __global__ __launch_bounds__(ST) void k_sort_hist(const K* __restrict__ keys, ui
 template<typename K, bool HAS_V, uint32_t DB>
 __global__ __launch_bounds__(ST) void k_sort_scatter(const K* __restrict__ kin, const uint32_t* __restrict__ vin,
                                                      K* __restrict__ kout, uint32_t* __restrict__ vout,
-                                                     uint64_t n, uint32_t shift, const uint32_t* __restrict__ offs, uint32_t nb)
+                                                     uint64_t n, uint32_t shift, uint32_t dmask, const uint32_t* __restrict__ offs, uint32_t nb)
 {
+	// dmask: the digit's bits, ND - 1, or fewer in the last pass of a sort whose end_bit lies inside the digit: bits the caller did not ask
+	// to sort on never reach a digit
 	// The tile is first ordered by digit in LDS (stable: wave by wave, ballot ranks inside a wave), then written out
 	// linearly: consecutive threads write consecutive elements of a bucket, so a bucket's share of the tile (16 keys on
 	// average) leaves as whole lines instead of one 4/8-byte store per lane and bucket.
@@ -82,7 +84,7 @@ __global__ __launch_bounds__(ST) void k_sort_scatter(const K* __restrict__ kin, 
 	{
 		uint64_t idx = wbase + (uint64_t)r * 64 + lane;
 		bool valid = idx < n;
-		uint32_t d = (uint32_t)(key[r] >> shift) & (ND - 1);
+		uint32_t d = (uint32_t)(key[r] >> shift) & dmask;
 		uint64_t peers = __ballot(valid);
 #pragma unroll
 		for (uint32_t b = 0; b < DB; ++b)
@@ -132,7 +134,7 @@ __global__ __launch_bounds__(ST) void k_sort_scatter(const K* __restrict__ kin, 
 		uint64_t idx = wbase + (uint64_t)r * 64 + lane;
 		if (idx < n)
 		{
-			uint32_t d = (uint32_t)(key[r] >> shift) & (ND - 1);
+			uint32_t d = (uint32_t)(key[r] >> shift) & dmask;
 			uint32_t lp = wh[w][d] + rank[r];
 			skey[lp] = key[r];
 			if (HAS_V) sval[lp] = val[r];
@@ -143,14 +145,14 @@ __global__ __launch_bounds__(ST) void k_sort_scatter(const K* __restrict__ kin, 
 	for (uint32_t j = threadIdx.x; j < tile_n; j += ST)
 	{
 		const K k = skey[j];
-		const uint32_t pos = gdelta[(uint32_t)(k >> shift) & (ND - 1)] + j;
+		const uint32_t pos = gdelta[(uint32_t)(k >> shift) & dmask] + j;
 		kout[pos] = k;
 		if (HAS_V) vout[pos] = sval[j];
 	}
 }
 
 template<typename K, uint32_t DB>
-cl_status sort_pass(cl_ctx* ctx, const K* kin, const uint32_t* vin, K* kout, uint32_t* vout, uint64_t n, uint32_t shift, uint32_t* hist, uint32_t nb)
+cl_status sort_pass(cl_ctx* ctx, const K* kin, const uint32_t* vin, K* kout, uint32_t* vout, uint64_t n, uint32_t shift, uint32_t dmask, uint32_t* hist, uint32_t nb)
 {
 	// (names as rocprofv3 prints the instantiations)
 	static const std::string kt = sizeof(K) == 8 ? "unsigned long" : "unsigned int", db = std::to_string(DB) + "u";
@@ -158,12 +160,12 @@ cl_status sort_pass(cl_ctx* ctx, const K* kin, const uint32_t* vin, K* kout, uin
 	// 9-bit 185 / 139 / 518 ms — 16 tiles of 512 counters are 32 KB of LDS and halve the blocks a CU holds)
 	constexpr uint32_t G = DB == 8 ? 16 : 4; const bool grouped = nb >= 4096;           // (16 M keys and more)
 	static const std::string n_hist1 = "k_sort_hist<" + kt + ", " + db + ", 1u>", n_histg = "k_sort_hist<" + kt + ", " + db + ", " + std::to_string(G) + "u>", n_sv = "k_sort_scatter<" + kt + ", true, " + db + ">", n_sk = "k_sort_scatter<" + kt + ", false, " + db + ">";
-	if (grouped) LAUNCHB_NAMED(ctx, n_histg.c_str(), n * sizeof(K), (k_sort_hist<K, DB, G>), (nb + G - 1) / G, ST, kin, n, shift, hist, nb);
-	else LAUNCHB_NAMED(ctx, n_hist1.c_str(), n * sizeof(K), (k_sort_hist<K, DB, 1>), nb, ST, kin, n, shift, hist, nb);
+	if (grouped) LAUNCHB_NAMED(ctx, n_histg.c_str(), n * sizeof(K), (k_sort_hist<K, DB, G>), (nb + G - 1) / G, ST, kin, n, shift, dmask, hist, nb);
+	else LAUNCHB_NAMED(ctx, n_hist1.c_str(), n * sizeof(K), (k_sort_hist<K, DB, 1>), nb, ST, kin, n, shift, dmask, hist, nb);
 	HIP_TRY(ctx, hipGetLastError());
 	CL_TRY(dev_exclusive_scan_u32(ctx, hist, (uint64_t)(1u << DB) * nb, nullptr));
-	if (vin) LAUNCHB_NAMED(ctx, n_sv.c_str(), n * (2 * sizeof(K) + 8), (k_sort_scatter<K, true, DB>), nb, ST, kin, vin, kout, vout, n, shift, (const uint32_t*)hist, nb);
-	else LAUNCHB_NAMED(ctx, n_sk.c_str(), n * 2 * sizeof(K), (k_sort_scatter<K, false, DB>), nb, ST, kin, (const uint32_t*)nullptr, kout, (uint32_t*)nullptr, n, shift, (const uint32_t*)hist, nb);
+	if (vin) LAUNCHB_NAMED(ctx, n_sv.c_str(), n * (2 * sizeof(K) + 8), (k_sort_scatter<K, true, DB>), nb, ST, kin, vin, kout, vout, n, shift, dmask, (const uint32_t*)hist, nb);
+	else LAUNCHB_NAMED(ctx, n_sk.c_str(), n * 2 * sizeof(K), (k_sort_scatter<K, false, DB>), nb, ST, kin, (const uint32_t*)nullptr, kout, (uint32_t*)nullptr, n, shift, dmask, (const uint32_t*)hist, nb);
 	HIP_TRY(ctx, hipGetLastError());
 	return CL_OK;
 }
@@ -199,11 +201,13 @@ cl_status sort_impl(cl_ctx* ctx, K* d_keys, uint32_t* d_vals, uint64_t n, uint32
 		if (n_pass & 1) { kout = pass == 0 ? ktmp2.p : (pass & 1) ? ktmp.p : d_keys; vout = pass == 0 ? vtmp2.p : (pass & 1) ? vtmp.p : d_vals; }
 		else { kout = (pass & 1) ? d_keys : ktmp.p; vout = (pass & 1) ? d_vals : vtmp.p; }
 		const uint32_t left = end_bit - shift, passes_left = n_pass_real - pass;
-		const uint32_t db = std::max(8u, (left + passes_left - 1) / passes_left); // (bits above end_bit in a digit are harmless only if they are equal: callers' keys are zero there or sorted on them anyway)
+		const uint32_t db = std::max(8u, (left + passes_left - 1) / passes_left);
 		const uint32_t use = std::min(db, 10u);
-		if (use == 10) CL_TRY((sort_pass<K, 10>(ctx, kin, vin, kout, vout, n, shift, hist.p, nb)));
-		else if (use == 9) CL_TRY((sort_pass<K, 9>(ctx, kin, vin, kout, vout, n, shift, hist.p, nb)));
-		else CL_TRY((sort_pass<K, 8>(ctx, kin, vin, kout, vout, n, shift, hist.p, nb)));
+		// a digit that reaches above end_bit (the last pass) is cut there: the order never depends on bits the caller did not ask to sort on
+		const uint32_t dmask = (1u << std::min(use, left)) - 1;
+		if (use == 10) CL_TRY((sort_pass<K, 10>(ctx, kin, vin, kout, vout, n, shift, dmask, hist.p, nb)));
+		else if (use == 9) CL_TRY((sort_pass<K, 9>(ctx, kin, vin, kout, vout, n, shift, dmask, hist.p, nb)));
+		else CL_TRY((sort_pass<K, 8>(ctx, kin, vin, kout, vout, n, shift, dmask, hist.p, nb)));
 		shift += use;
 		kin = kout; vin = vout;
 	}
