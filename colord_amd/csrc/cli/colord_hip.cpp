@@ -1,5 +1,5 @@
 // colord_hip — command-line tool on top of libcolord_hip.so with the reference's sub-commands (src/colord/main.cpp,
-// arg_parse.cpp): compress-ont | compress-pbhifi | compress-pbraw (compress.cpp: GPU data path), decompress and info
+// arg_parse.cpp): compress-ont | compress-pbhifi | compress-pbraw (compress.cpp, compress_multi.cpp: GPU data path), decompress and info
 // (decompress.cpp: host decoders of the library).  Archives are interchangeable with the reference's in both directions.
 #include <cstdio>
 #include <cstdlib>
@@ -8,8 +8,8 @@
 int run_compress(int argc, char** argv);        // compress.cpp
 int run_decompress(int argc, char** argv);      // decompress.cpp
 int run_info(int argc, char** argv);
-int run_parse_check(int argc, char** argv);     // compress.cpp: the input reader alone (test aid, no GPU)
-int run_rccl_selftest(int argc, char** argv);   // compress.cpp: the collectives of the multi-GPU host over RCCL
+int run_parse_check(int argc, char** argv);     // parse_check.cpp: the input reader alone (test aid, no GPU)
+int run_rccl_selftest(int argc, char** argv);   // compress_multi.cpp: the collectives of the multi-GPU host over RCCL
 
 int main(int argc, char** argv)
 {

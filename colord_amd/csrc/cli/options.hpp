@@ -1,0 +1,142 @@
+// options.hpp — the options of `colord_hip compress-*`: the reference's (src/colord/arg_parse.cpp:455-640 options and their checks, :89-408
+// presets, :32-84,410-450 quality thresholds) and this build's own.  Both drivers (compress.cpp, compress_multi.cpp) start from parse_options().
+#pragma once
+#include "archive.hpp"
+#include <cctype>
+#include <cstdlib>
+
+struct Preset { int level; uint32_t ci, cs, f, c, max_rec, min_part_alt; int qual_mode; int sparse; double g; };
+// arg_parse.cpp:89-408 — [source][priority]: ratio, balanced, memory (memory is the default priority)
+inline const Preset PRESETS[3][3] = {
+	{ { 3, 2, 120, 8, 10, 6, 48, 2, 0, 1 }, { 2, 3, 100, 9, 8, 5, 48, 2, 1, 2 }, { 1, 4, 80, 12, 5, 3, 64, 2, 1, 1 } },          // ONT, 4-avg qualities
+	{ { 3, 2, 120, 8, 10, 6, 48, 8, 0, 1 }, { 2, 3, 100, 9, 8, 5, 48, 8, 1, 2 }, { 1, 4, 80, 12, 5, 3, 64, 8, 1, 1 } },          // PBRaw, qualities dropped
+	{ { 3, 2, 150, 20, 12, 6, 48, 1, 0, 1 }, { 2, 3, 120, 30, 10, 5, 48, 1, 1, 6 }, { 2, 3, 100, 40, 8, 5, 48, 1, 1, 3 } },       // PBHiFi, 5-avg qualities
+};
+// default -T / -D values of the quality modes (arg_parse.cpp:32-84,410-450): mode -> forward thresholds, decoder representatives
+struct QDef { std::vector<uint32_t> fwd, rev; };
+inline QDef qual_defaults(int mode)
+{
+	static const QDef defs[9] = { {}, { { 7, 14, 26, 93 }, {} }, { { 7, 14, 26 }, {} }, { { 7 }, {} }, { { 7, 14, 26, 93 }, { 3, 10, 18, 35, 93 } }, { { 7, 14, 26 }, { 3, 10, 18, 35 } }, { { 7 }, { 1, 13 } }, {}, { {}, { 0 } } };
+	return defs[mode];
+}
+inline const char* const QUAL_MODE_NAMES[9] = { "org", "5-avg", "4-avg", "2-avg", "5-fix", "4-fix", "2-fix", "avg", "none" };      // QualityComprMode (params.h:33-43)
+inline int qual_mode_of(const std::string& s) { for (int i = 0; i < 9; ++i) if (s == QUAL_MODE_NAMES[i]) return i; return -1; }
+inline std::vector<uint32_t> list_u32(const std::string& s) { std::vector<uint32_t> v; size_t p = 0; while (p < s.size()) { size_t e = s.find_first_of(", ", p); if (e == std::string::npos) e = s.size(); if (e > p) v.push_back((uint32_t)strtoul(s.substr(p, e - p).c_str(), nullptr, 10)); p = e + 1; } return v; }
+
+struct Options {
+	int source = 0, prio = 2, gpu = 0; bool verbose = false;
+	uint32_t k = 0, a = 0; std::string in, out, genome; bool store_genome = false;
+	long ci = -1, cs = -1, f = -1, c = -1, max_rec = -1, min_to_alt = -1, min_anchors = 1;
+	double cost_mult = 1.0, frac_min = 0.5, frac_always = 0.9, max_matches_mult = 10.0, g = -1, exponent = 1.0;
+	int qual_mode = -1, header_mode = 0, ref_mode = -1;
+	std::vector<uint32_t> T, D; bool has_T = false, has_D = false;
+	double chunk_bases = 1.0e9; bool chunk_bases_set = false;
+	uint64_t part_symbols = 2u << 21;               // --part-symbols: the coder parts close once their reads (+ 1 guard each) reach this; default = the reader packs (defs.h:45)
+	int parse_threads = 0;                          // --parse-threads (0: as many as the host offers, at most 32)
+	bool stream_input = false;                      // --stream-input: the input is read three times (k-mers, reference reads, coding) and only a window of chunks is resident in HBM
+	int domains = 1;                                // --domains K: K INDEPENDENT model domains on one GPU (own k-mer set, references, index, models each): decoded side by side
+	int gpus = 1; std::vector<int> gpu_list; std::string transport = "rccl";   // --gpus N [--gpu-list a,b,..] [--transport rccl|host]: reads sharded over N GPUs (run_compress_multi)
+	Preset P{}; QDef qd;                            // resolved by parse_options: the preset of source and priority with the options laid over it, the quality thresholds / representatives
+	int argc = 0; char** argv = nullptr;            // the command line as given (`info` stream)
+};
+
+inline void usage()
+{
+	fprintf(stderr,
+		"usage: colord_hip compress-ont|compress-pbhifi|compress-pbraw [options] input.fastq|fasta[.gz] output.colord\n"
+		"       colord_hip decompress archive.colord output.fastq\n       colord_hip info archive.colord\n"
+		"options (as the reference, arg_parse.cpp:455-640):\n"
+		"  -p,--priority ratio|balanced|memory   -k,--kmer-len K with -a,--anchor-len A (both or none)\n"
+		"  -q,--qual org|none|avg|2-fix|4-fix|5-fix|2-avg|4-avg|5-avg   -T,--qual-thresholds a,b,..   -D,--qual-values a,b,..\n"
+		"  -i,--identifier org|main|none   -c,--max-candidates N   -L,--Lowest-count N   -H,--Highest-count N   -f,--filter-modulo N\n"
+		"  -e,--edit-script-mult X   -r,--max-recurence-level N   --min-to-alt N   --min-mmer-frac X   --min-mmer-force-enc X\n"
+		"  --max-matches-mult X   --min-anchors N   -R,--Ref-reads-mode all|sparse   -g,--sparse-range X   -x,--sparse-exponent X\n"
+		"  -t,--threads N (accepted; the data path runs on the GPU)   -v,--verbose   --gpu N   --chunk-bases X\n"
+		"  --part-symbols N   coder parts of N symbols instead of the reference's 4194304 (defs.h:45): same FASTQ back from either\n"
+		"                     decompressor, 8 more bytes per part, far shorter interval-coder chains (65536: +0.04 %% size, 1.4x the speed)\n"
+		"  --parse-threads N  threads that index a plain FASTQ (default: the host's, at most 32)\n"
+		"  --stream-input     bounded device memory: the input is read three times (k-mers, reference reads, coding) and only a window of\n"
+		"                     four chunks is resident at a time instead of the whole input (same archive)\n"
+		"  --domains K        K independent model domains (equal shares of the reads, each compressed on its own): `colord_hip decompress`\n"
+		"                     decodes them side by side; costs archive size (own k-mer statistics and reference reads per domain)\n"
+		"  --gpus N [--gpu-list a,b,..] [--transport rccl|host]   reads sharded over N GPUs, one host thread and one model domain per GPU;\n"
+		"                     the k-mer set, reference reads and index are replicated through RCCL (or host staging: several ranks per GPU)\n");
+}
+
+// the command line of a compress-* mode with every check of the reference (arg_parse.cpp:604-625) and of this build; -h ends the process
+inline Options parse_options(int argc, char** argv)
+{
+	Options O; O.argc = argc; O.argv = argv;
+	const std::string mode = argv[1];
+	O.source = mode == "compress-ont" ? 0 : mode == "compress-pbraw" ? 1 : mode == "compress-pbhifi" ? 2 : -1;
+	if (O.source < 0) { usage(); die("unknown mode " + mode); }
+	std::vector<std::string> pos;
+	auto need = [&](int& i) -> std::string { if (i + 1 >= argc) die(std::string("option ") + argv[i] + " needs a value"); return argv[++i]; };
+	// (-T 5 12 30: values separated by spaces are taken as long as two positional arguments remain)
+	auto more_values = [&](int& i, std::vector<uint32_t>& v) { while (i + 1 < argc && isdigit((unsigned char)argv[i + 1][0]) && pos.size() + (size_t)(argc - i - 1) > 2) v.push_back((uint32_t)atoi(argv[++i])); };
+	for (int i = 2; i < argc; ++i)
+	{
+		const std::string a = argv[i];
+		if (a == "-p" || a == "--priority") { const std::string v = need(i); O.prio = v == "ratio" ? 0 : v == "balanced" ? 1 : v == "memory" ? 2 : -1; if (O.prio < 0) die("unknown priority " + v); }
+		else if (a == "-k" || a == "--kmer-len") { O.k = (uint32_t)atoi(need(i).c_str()); if (O.k < 15 || O.k > 28) die("-k,--kmer-len must be in [15, 28]"); }
+		else if (a == "-a" || a == "--anchor-len") O.a = (uint32_t)atoi(need(i).c_str());
+		else if (a == "-q" || a == "--qual") { const std::string v = need(i); O.qual_mode = qual_mode_of(v); if (O.qual_mode < 0) die("unknown quality mode " + v); }
+		else if (a == "-T" || a == "--qual-thresholds") { O.T = list_u32(need(i)); O.has_T = true; more_values(i, O.T); }
+		else if (a == "-D" || a == "--qual-values") { O.D = list_u32(need(i)); O.has_D = true; more_values(i, O.D); }
+		else if (a == "-i" || a == "--identifier") { const std::string v = need(i); O.header_mode = v == "org" ? 0 : v == "main" ? 1 : v == "none" ? 2 : -1; if (O.header_mode < 0) die("unknown header mode " + v); }
+		else if (a == "-c" || a == "--max-candidates") { O.c = atol(need(i).c_str()); if (O.c < 1) die("-c must be positive"); }
+		else if (a == "-L" || a == "--Lowest-count") O.ci = atol(need(i).c_str());
+		else if (a == "-H" || a == "--Highest-count") O.cs = atol(need(i).c_str());
+		else if (a == "-f" || a == "--filter-modulo") { O.f = atol(need(i).c_str()); if (O.f < 1) die("-f must be positive"); }
+		else if (a == "-e" || a == "--edit-script-mult") O.cost_mult = atof(need(i).c_str());
+		else if (a == "-r" || a == "--max-recurence-level") O.max_rec = atol(need(i).c_str());
+		else if (a == "--min-to-alt") O.min_to_alt = atol(need(i).c_str());
+		else if (a == "--min-mmer-frac") O.frac_min = atof(need(i).c_str());
+		else if (a == "--min-mmer-force-enc") O.frac_always = atof(need(i).c_str());
+		else if (a == "--max-matches-mult") O.max_matches_mult = atof(need(i).c_str());
+		else if (a == "--min-anchors") O.min_anchors = atol(need(i).c_str());
+		else if (a == "-R" || a == "--Ref-reads-mode") { const std::string v = need(i); O.ref_mode = v == "all" ? 0 : v == "sparse" ? 1 : -1; if (O.ref_mode < 0) die("unknown reference reads mode " + v); }
+		else if (a == "-g" || a == "--sparse-range") O.g = atof(need(i).c_str());
+		else if (a == "-x" || a == "--sparse-exponent") O.exponent = atof(need(i).c_str());
+		else if (a == "-t" || a == "--threads") (void)need(i);
+		else if (a == "--fill-factor-filtered-kmers" || a == "--fill-factor-kmers-to-reads") (void)need(i);     // host hash-table tuning of the reference: no counterpart here
+		else if (a == "-v" || a == "--verbose") O.verbose = true;
+		else if (a == "-G" || a == "--reference-genome") O.genome = need(i);
+		else if (a == "-s" || a == "--store-reference") O.store_genome = true;
+		else if (a == "--gpu") O.gpu = atoi(need(i).c_str());
+		else if (a == "--gpus") { O.gpus = atoi(need(i).c_str()); if (O.gpus < 1 || O.gpus > 64) die("--gpus must be in [1, 64]"); }
+		else if (a == "--domains") { O.domains = atoi(need(i).c_str()); if (O.domains < 1 || O.domains > 1024) die("--domains must be in [1, 1024]"); }
+		else if (a == "--gpu-list") { for (uint32_t v : list_u32(need(i))) O.gpu_list.push_back((int)v); }
+		else if (a == "--transport") { O.transport = need(i); if (O.transport != "rccl" && O.transport != "host") die("--transport must be rccl or host"); }
+		else if (a == "--chunk-bases") { O.chunk_bases = atof(need(i).c_str()); O.chunk_bases_set = true; }
+		else if (a == "--part-symbols") { O.part_symbols = strtoull(need(i).c_str(), nullptr, 10); if (O.part_symbols < 1024 || O.part_symbols > (2u << 21)) die("--part-symbols must be in [1024, 4194304]"); }
+		else if (a == "--stream-input") O.stream_input = true;
+		else if (a == "--parse-threads") { O.parse_threads = atoi(need(i).c_str()); if (O.parse_threads < 1 || O.parse_threads > 256) die("--parse-threads must be in [1, 256]"); }
+		else if (a == "-h" || a == "--help") { usage(); exit(0); }
+		else if (!a.empty() && a[0] == '-' && a.size() > 1) die("unknown option " + a);
+		else pos.push_back(a);
+	}
+	if (pos.size() != 2) { usage(); die("expected input and output paths"); }
+	O.in = pos[0]; O.out = pos[1];
+	// the checks of arg_parse.cpp:604-625
+	if (O.k && !O.a) die("if -k,--kmer-len is set -a,--anchor-len also must be set");
+	if (!O.k && O.a) die("if -a,--anchor-len is set -k,--kmer-len also must be set");
+	if (O.k && O.a > O.k) die("-a,--anchor-len must be less than or equal to -k,--kmer-len");
+	Preset& P = O.P; P = PRESETS[O.source][O.prio];
+	auto over = [](uint32_t& dst, long v) { if (v >= 0) dst = (uint32_t)v; };
+	over(P.ci, O.ci); over(P.cs, O.cs); over(P.f, O.f); over(P.c, O.c); over(P.max_rec, O.max_rec); over(P.min_part_alt, O.min_to_alt);
+	if (O.qual_mode >= 0) P.qual_mode = O.qual_mode;
+	if (O.ref_mode >= 0) P.sparse = O.ref_mode;
+	if (O.g >= 0) P.g = O.g;
+	if (P.c > 64) die("-c,--max-candidates above 64 is not supported by the DNA coder of this build");
+	// quality thresholds / representatives (adjust_quality_mode_and_thresholds, arg_parse.cpp:410-450)
+	QDef& qd = O.qd; qd = qual_defaults(P.qual_mode);
+	const std::string qname = QUAL_MODE_NAMES[P.qual_mode];
+	if (O.has_T) { if (qd.fwd.empty()) die("-T,--qual-thresholds is not allowed for '" + qname + "' quality mode"); if (O.T.size() != qd.fwd.size()) die("for '" + qname + "' quality compression mode expected number of quality thresholds is " + std::to_string(qd.fwd.size()) + ", but " + std::to_string(O.T.size()) + " given."); qd.fwd = O.T; }
+	if (O.has_D) { if (qd.rev.empty()) die("-D,--qual-values is not allowed for '" + qname + "' quality mode"); if (O.D.size() != qd.rev.size()) die("for '" + qname + "' quality compression mode expected number of quality values is " + std::to_string(qd.rev.size()) + ", but " + std::to_string(O.D.size()) + " given."); qd.rev = O.D; }
+	for (size_t i = 0; i < qd.fwd.size(); ++i) if (qd.fwd[i] > 95 || (i && qd.fwd[i] < qd.fwd[i - 1])) die("quality thresholds must be ascending values in [0, 95]");
+	if (!O.gpu_list.empty() && O.gpus == 1) O.gpus = (int)O.gpu_list.size();
+	if (O.domains > 1 && O.gpus > 1) die("--domains and --gpus exclude each other (every GPU is a model domain already)");
+	if (O.stream_input && O.domains > 1) die("--stream-input is not available with --domains");
+	return O;
+}

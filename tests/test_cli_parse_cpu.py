@@ -1,4 +1,4 @@
-"""The command-line compressor's input reader without a GPU (`colord_hip parse-check`, csrc/cli/compress.cpp): a plain FASTQ is indexed
+"""The command-line compressor's input reader without a GPU (`colord_hip parse-check`, csrc/cli/fastx_input.hpp, parse_check.cpp): a plain FASTQ is indexed
 by several threads over byte ranges of the mapped file and the chunks are filled by parallel copies; what the compressor is handed —
 bases, qualities, offsets, reader packs (in_reads.cpp:62-77), coder parts (--part-symbols), ids — must be exactly what the
 sequential reader returns, on the inputs the reference's reader accepts (in_reads.cpp:79-92,188-226: CR LF, blank lines, a last line

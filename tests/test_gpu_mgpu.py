@@ -165,7 +165,7 @@ def test_reference_genome_mode_with_sharded_reads(tmp_path, stored):
     assert sum(len(p) for _, p in b["dna"].parts) < one * 1.5           # a genome-less second rank would lose far more than a model restart
 
 
-# ---- the C++ multi-GPU host: `colord_hip compress-* --gpus N` (csrc/cli/compress.cpp run_compress_multi, cli/transport.hpp) ------------
+# ---- the C++ multi-GPU host: `colord_hip compress-* --gpus N` (csrc/cli/compress_multi.cpp run_compress_multi, cli/transport.hpp) ------------
 def test_cpp_rccl_transport_selftest():
     """The three collectives behind cl_exchange over RCCL directly (ncclCommInitAll, grouped send / recv): a communicator of ONE rank
     on this box's one GPU still runs the RCCL code path — uneven and empty shares, every byte checked."""
