@@ -1267,7 +1267,7 @@ cl_status dna_group_prepare(cl_ctx* ctx, cl_dna_coder* D, DnaWalked& W, uint32_t
 }
 } // namespace
 
-// Internal (stream.hip): everything of a batch that needs no model state — the walks and, with part bounds, the sorted groups — on
+// Internal (lookahead.hip): everything of a batch that needs no model state — the walks and, with part bounds, the sorted groups — on
 // ANY context (the compressor runs it on a context and thread of its own beside the coding of the batch before).  The two scalars
 // the walk starts from chain batch to batch: the caller keeps them (cl_dna_coder_state for the first batch).
 cl_status cl_dna_prepare_batch(cl_ctx* ctx, cl_dna_coder* D, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, const uint32_t* d_es_ntuples, uint32_t n_reads,
@@ -1329,7 +1329,7 @@ void cl_dna_walked_free(DnaWalked* W) { delete W; }
 void cl_dna_set_ahead(cl_dna_coder* D, DnaWalked* W) { if (D) D->ahead.reset(W); else delete W; }
 void cl_dna_coder_state(const cl_dna_coder* D, uint32_t* prev_types, uint32_t* read_id) { if (prev_types) *prev_types = D->prev_types; if (read_id) *read_id = D->cur_read_id; }
 
-// Internal (stream.hip): the walk of the batch that FOLLOWS the one being coded, from inside cl_dna_encode's before_tail hook.
+// Internal (lookahead.hip): the walk of the batch that FOLLOWS the one being coded, from inside cl_dna_encode's before_tail hook.
 cl_status cl_dna_walk_ahead(cl_ctx* ctx, cl_dna_coder* D, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, const uint32_t* d_es_ntuples, uint32_t n_reads)
 {
 	if (!ctx || !D || !refs || !d_es || !d_es_off || !d_es_ntuples || !n_reads) return CL_E_INVALID;
@@ -1440,7 +1440,7 @@ cl_status dna_evolve_batch(cl_ctx* ctx, cl_dna_coder* D, const cl_reads* refs, c
 }
 } // namespace
 
-// Internal (stream.hip): the model half of the batch that FOLLOWS the one being coded, from inside cl_dna_encode's before_tail hook:
+// Internal (lookahead.hip): the model half of the batch that FOLLOWS the one being coded, from inside cl_dna_encode's before_tail hook:
 // W is that batch, walked (and sorted) ahead by cl_dna_prepare_batch; the next cl_dna_encode finds its coders running already.
 cl_status cl_dna_evolve_ahead(cl_ctx* ctx, cl_dna_coder* D, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, const uint32_t* d_es_ntuples, uint32_t n_reads,
                               const uint32_t* h_part_bounds, uint32_t n_parts, DnaWalked* W)

@@ -584,7 +584,7 @@ cl_status qual_prepare(cl_ctx* ctx, cl_qual_coder* Q, const cl_reads* R, const u
 	return CL_OK;
 }
 } // namespace
-// Internal (stream.hip): the model-independent half of cl_qual_encode for a batch, on any context; cl_qual_set_ahead hands it to
+// Internal (lookahead.hip): the model-independent half of cl_qual_encode for a batch, on any context; cl_qual_set_ahead hands it to
 // the coder, whose next cl_qual_encode uses it if it is the batch (arena, qualities, part bounds) it was made for.
 cl_status cl_qual_prepare_batch(cl_ctx* ctx, cl_qual_coder* Q, const cl_reads* R, const uint8_t* d_quals, const uint64_t* d_qual_off,
                                 const uint8_t* d_flags, const uint32_t* h_part_bounds, uint32_t n_parts, QualPrepared** out)
@@ -669,7 +669,7 @@ cl_status qual_evolve_batch(cl_ctx* ctx, cl_qual_coder* Q, const cl_reads* R, co
 	return CL_OK;
 }
 } // namespace
-// Internal (stream.hip): the model half of the batch that FOLLOWS the one being coded, from cl_qual_encode's before_tail hook
+// Internal (lookahead.hip): the model half of the batch that FOLLOWS the one being coded, from cl_qual_encode's before_tail hook
 cl_status cl_qual_evolve_ahead(cl_ctx* ctx, cl_qual_coder* Q, const cl_reads* R, const uint8_t* d_quals, const uint64_t* d_qual_off, const uint32_t* h_part_bounds, uint32_t n_parts, QualPrepared* P)
 {
 	std::unique_ptr<QualPrepared> Pp(P);

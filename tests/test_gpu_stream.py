@@ -1,7 +1,9 @@
-"""GPU parity suite for the chunked compressor (csrc/stream.hip, cl_compressor_*): an input presented chunk by chunk —
-pass 1 over all chunks, reference listing over all chunks, pass 2 chunk by chunk with persistent coders — must give the
-`dna` and `qual` parts of ONE cl_compress_shard call over the whole input, byte for byte (a read sees the
-index entries of earlier reference reads only, so cutting the input in file order changes nothing).  cl_compress_shard
+"""GPU parity suite for the chunked compressor (cl_compressor_*: csrc/stream.hip, its look-ahead csrc/lookahead.hip): an
+input presented chunk by chunk — pass 1 over all chunks, reference listing over all chunks, pass 2 chunk by chunk with
+persistent coders — must give the `dna` and `qual` parts of ONE cl_compress_shard call (csrc/driver.hip) over the whole
+input, byte for byte (a read sees the index entries of earlier reference reads only, so cutting the input in
+file order changes nothing).  The two share their steps (csrc/pass_steps.hpp) but build the index two ways — over all lists
+in one call there, over pairs gathered chunk by chunk here — which is what makes the comparison a proof.  cl_compress_shard
 itself is pinned to the reference's bytes by test_gpu_encode / test_gpu_roundtrip / test_gpu_cli.
 
 Also here: exact counting of k-mers key range by key range (inputs of 2^32 and more k-mers take that path; the
