@@ -13,7 +13,7 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COLORD_HIP_LIBRARY") or os.path.join(_HERE, "libcolord_hip.so")    # (COLORD_HIP_LIBRARY: another build of the same library, for A/B measurements)
 
-CL_OK, CL_E_INVALID, CL_E_HIP, CL_E_CAPACITY, CL_E_NOMEM, CL_E_UNSUPPORTED = 0, -1, -2, -3, -4, -5
+CL_OK, CL_E_INVALID, CL_E_HIP, CL_E_CAPACITY, CL_E_NOMEM, CL_E_UNSUPPORTED, CL_E_MISMATCH = 0, -1, -2, -3, -4, -5, -6
 
 
 class ColordHipError(RuntimeError):
@@ -64,6 +64,11 @@ _SIG = {
     "cl_ctx_stream": (_P, [_P]),
     "cl_ctx_last_kernel_ms": (C.c_int32, [_P, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     "cl_ctx_set_timing": (None, [_P, C.c_int]),
+    "cl_ctx_set_verify": (None, [_P, C.c_int]),
+    "cl_ctx_verified": (C.c_int32, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cl_es_expand": (C.c_int32, [_P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
+    "cl_es_verify": (C.c_int32, [_P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "cl_compressor_verified": (C.c_int32, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cl_ctx_kernel_times": (C.c_int32, [_P, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cl_reads_pack": (C.c_int32, [_P, _P, _P, C.c_uint32, C.c_int, C.POINTER(_P)]),
     "cl_reads_free": (None, [_P]),

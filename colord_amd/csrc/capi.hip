@@ -125,6 +125,16 @@ extern "C" void cl_ctx_destroy(cl_ctx* c)
 extern "C" const char* cl_last_error(const cl_ctx* c) { return c ? c->err.c_str() : "null context"; }
 extern "C" void* cl_ctx_stream(cl_ctx* c) { return c ? (void*)c->stream : nullptr; }
 extern "C" void cl_ctx_set_timing(cl_ctx* c, int on) { if (c) c->timing = on != 0; }
+extern "C" void cl_ctx_set_verify(cl_ctx* c, int on) { if (c) c->verify = on != 0; }
+extern "C" cl_status cl_ctx_verified(const cl_ctx* c, uint64_t* reads, uint64_t* bases)
+{
+	if (!c) return CL_E_INVALID;
+	uint64_t r = c->verified_reads.load(), b = c->verified_bases.load();
+	for (const cl_ctx* l : c->lanes) { r += l->verified_reads.load(); b += l->verified_bases.load(); }     // (encode lanes of a compressor on this context)
+	if (reads) *reads = r;
+	if (bases) *bases = b;
+	return CL_OK;
+}
 extern "C" cl_status cl_ctx_last_kernel_ms(const cl_ctx* c, const char* kernel, double* ms, uint32_t* launches)
 {
 	if (!c || !kernel) return CL_E_INVALID;

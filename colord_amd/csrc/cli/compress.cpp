@@ -196,6 +196,7 @@ int run_compress(int argc, char** argv)
 	const Params prm = make_params(O, ka);
 	const bool with_qual = R.fastq;
 	cl_compressor* cmp = nullptr;
+	if (O.verify_scripts) cl_ctx_set_verify(ctx, 1);
 	ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, nullptr, estimated_bases(R), &cmp), "cl_compressor_create");
 	GenomeMode GM;
 	if (!O.genome.empty()) { GM.read(O); GM.count_kmers(ctx, cmp); }
@@ -275,7 +276,7 @@ int run_compress(int argc, char** argv)
 		std::vector<uint64_t> dsz(np), qsz(np); cl_compress_info info{};
 		PartWriter::Set& out = pw.acquire(ci);
 		const auto te = std::chrono::steady_clock::now();
-		ck(ctx, cl_compressor_encode(cmp, dc.reads, dc.d_quals, dc.d_off, dc.parts.data(), np, dc.packs.data(), (uint32_t)dc.packs.size() - 1, out.d_dna, pw.cap.dna, dsz.data(), out.d_qual, pw.cap.qual, qsz.data(), &info), "pass 2");
+		ck_encode(ctx, cl_compressor_encode(cmp, dc.reads, dc.d_quals, dc.d_off, dc.parts.data(), np, dc.packs.data(), (uint32_t)dc.packs.size() - 1, out.d_dna, pw.cap.dna, dsz.data(), out.d_qual, pw.cap.qual, qsz.data(), &info), O.out);
 		t_encode += std::chrono::duration<double>(std::chrono::steady_clock::now() - te).count();
 		pw.submit(ci, std::move(dsz), std::move(qsz), info);
 		dna_total += info.dna_bytes; qual_total += info.qual_bytes; n_parts_total += np;
@@ -293,6 +294,7 @@ int run_compress(int argc, char** argv)
 	else if (getenv("COLORD_HIP_FULL_TEARDOWN")) for (DevChunk& dc : chunks) up.release(dc);
 	pw.release();
 	lap("pass 2 (dna + qual parts written)");
+	verified_line(O, cmp);
 
 	// tail: header, meta (compression.cpp:704-779), info (utils.cpp:326-342)
 	hdr.join();

@@ -10,6 +10,20 @@
 #include <mutex>
 
 inline void ck(cl_ctx* ctx, cl_status s, const char* what) { if (s != CL_OK) die(std::string(what) + ": " + (ctx ? cl_last_error(ctx) : "error")); }
+// a failed encode call of pass 2 (--verify-scripts: a read that its edit script does not rebuild): what is on disk is half a file and goes with the message
+inline void ck_encode(cl_ctx* ctx, cl_status s, const std::string& out_path)
+{
+	if (s == CL_OK) return;
+	(void)remove(out_path.c_str());
+	die(std::string("pass 2: ") + cl_last_error(ctx) + " (no archive was written)");
+}
+// -v with --verify-scripts: what the compressor's contexts checked
+inline void verified_line(const Options& O, cl_compressor* cmp, const char* who = "")
+{
+	if (!O.verify_scripts || !O.verbose) return;
+	uint64_t r = 0, b = 0;
+	if (cl_compressor_verified(cmp, &r, &b) == CL_OK) fprintf(stderr, "# edit scripts verified%s: %llu reads, %llu bases rebuilt on the device and equal to the input\n", who, (unsigned long long)r, (unsigned long long)b);
+}
 template<class T> void le(std::vector<uint8_t>& v, T x) { for (size_t i = 0; i < sizeof(T); ++i) v.push_back((uint8_t)((uint64_t)x >> (8 * i))); }
 inline void le_double(std::vector<uint8_t>& v, double d) { uint64_t u; memcpy(&u, &d, 8); le(v, u); }
 // -v: seconds since the start of the run in front of every step

@@ -107,6 +107,7 @@ int run_compress_multi(const Options& O)
 		uint64_t my_bases = 0; for (uint64_t i = r0; i < r1; ++i) my_bases += S.len(i);
 		cl_exchange X; if (T) X = T->exchange();
 		cl_compressor* cmp = nullptr;
+		if (O.verify_scripts) cl_ctx_set_verify(ctx, 1);
 		ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, T ? &X : nullptr, my_bases, &cmp), "cl_compressor_create");
 		if (GM.on) GM.count_kmers(ctx, cmp);
 		// chunks of whole reader packs (the packs are cut from this rank's first read on: in_reads.cpp:62-77).  The chunk size follows the
@@ -170,7 +171,7 @@ int run_compress_multi(const Options& O)
 			}
 			const uint32_t np = (uint32_t)dc.parts.size() - 1;
 			std::vector<uint64_t> dsz(np), qsz(np); cl_compress_info info{};
-			ck(ctx, cl_compressor_encode(cmp, dc.reads, dc.d_quals, dc.d_off, dc.parts.data(), np, dc.packs.data(), (uint32_t)dc.packs.size() - 1, d_dna, cap.dna, dsz.data(), d_qual, cap.qual, qsz.data(), &info), "pass 2");
+			ck_encode(ctx, cl_compressor_encode(cmp, dc.reads, dc.d_quals, dc.d_off, dc.parts.data(), np, dc.packs.data(), (uint32_t)dc.packs.size() - 1, d_dna, cap.dna, dsz.data(), d_qual, cap.qual, qsz.data(), &info), O.out);
 			const size_t od = RO.dna.size(), oq = RO.qual.size();
 			RO.dna.resize(od + info.dna_bytes); RO.qual.resize(oq + info.qual_bytes);
 			if (info.dna_bytes) hipck(hipMemcpy(RO.dna.data() + od, d_dna, info.dna_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
@@ -217,6 +218,7 @@ int run_compress_multi(const Options& O)
 		write_parts(RO.dna_base, RO.dna, RO.dsz, true);
 		if (with_qual) write_parts(RO.qual_base, RO.qual, RO.qsz, false);
 		RO.moved = T ? T->bytes_moved : 0;
+		verified_line(O, cmp, (" (rank " + std::to_string(rank) + ")").c_str());
 		cl_compressor_free(cmp);
 		cl_ctx_destroy(qctx); cl_ctx_destroy(ctx);
 	};

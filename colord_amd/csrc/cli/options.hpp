@@ -35,6 +35,7 @@ struct Options {
 	int parse_threads = 0;                          // --parse-threads (0: as many as the host offers, at most 32)
 	bool stream_input = false;                      // --stream-input: the input is read three times (k-mers, reference reads, coding) and only a window of chunks is resident in HBM
 	int domains = 1;                                // --domains K: K INDEPENDENT model domains on one GPU (own k-mer set, references, index, models each): decoded side by side
+	bool verify_scripts = false;                    // --verify-scripts: cl_ctx_set_verify on every compressor's context
 	int gpus = 1; std::vector<int> gpu_list; std::string transport = "rccl";   // --gpus N [--gpu-list a,b,..] [--transport rccl|host]: reads sharded over N GPUs (run_compress_multi)
 	Preset P{}; QDef qd;                            // resolved by parse_options: the preset of source and priority with the options laid over it, the quality thresholds / representatives
 	int argc = 0; char** argv = nullptr;            // the command line as given (`info` stream)
@@ -57,6 +58,8 @@ inline void usage()
 		"  --parse-threads N  threads that index a plain FASTQ (default: the host's, at most 32)\n"
 		"  --stream-input     bounded device memory: the input is read three times (k-mers, reference reads, coding) and only a window of\n"
 		"                     four chunks is resident at a time instead of the whole input (same archive)\n"
+		"  --verify-scripts   every read is rebuilt on the device from its edit script and the reference reads and compared with the input; the entropy-coded bytes are not decoded\n"
+		"                     (a read that differs: message, no archive, non-zero exit)\n"
 		"  --domains K        K independent model domains (equal shares of the reads, each compressed on its own): `colord_hip decompress`\n"
 		"                     decodes them side by side; costs archive size (own k-mer statistics and reference reads per domain)\n"
 		"  --gpus N [--gpu-list a,b,..] [--transport rccl|host]   reads sharded over N GPUs, one host thread and one model domain per GPU;\n"
@@ -111,6 +114,7 @@ inline Options parse_options(int argc, char** argv)
 		else if (a == "--chunk-bases") { O.chunk_bases = atof(need(i).c_str()); O.chunk_bases_set = true; }
 		else if (a == "--part-symbols") { O.part_symbols = strtoull(need(i).c_str(), nullptr, 10); if (O.part_symbols < 1024 || O.part_symbols > (2u << 21)) die("--part-symbols must be in [1024, 4194304]"); }
 		else if (a == "--stream-input") O.stream_input = true;
+		else if (a == "--verify-scripts") O.verify_scripts = true;
 		else if (a == "--parse-threads") { O.parse_threads = atoi(need(i).c_str()); if (O.parse_threads < 1 || O.parse_threads > 256) die("--parse-threads must be in [1, 256]"); }
 		else if (a == "-h" || a == "--help") { usage(); exit(0); }
 		else if (!a.empty() && a[0] == '-' && a.size() > 1) die("unknown option " + a);

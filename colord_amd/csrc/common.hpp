@@ -342,6 +342,8 @@ struct cl_ctx {
 	std::atomic<hipStream_t> side3{ nullptr };    // fourth stream: the giant gaps
 	std::string err;
 	bool timing = false;
+	bool verify = false;                         // cl_ctx_set_verify: tuple_streams (pass_steps.hpp) rebuilds every read from its edit script and compares it with the input
+	std::atomic<uint64_t> verified_reads{ 0 }, verified_bases{ 0 };   // what this context has checked so (cl_ctx_verified adds the encode lanes')
 	std::map<std::string, KernelTime> times;     // per-kernel accumulated HIP-event time of the last API call
 	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
 	std::vector<double> pending_bytes, pending_cells;

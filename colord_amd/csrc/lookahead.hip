@@ -34,6 +34,7 @@ template<class Ready> static bool wait_ready(LookAhead& la, std::unique_lock<std
 template<class Work> static cl_status work_on(cl_compressor* c, cl_ctx* ctx, Work work)
 {
 	ctx->timing = c->ctx->timing;
+	ctx->verify = c->ctx->verify;
 	const cl_status s = work();
 	cl_timing_collect(ctx);
 	return s;

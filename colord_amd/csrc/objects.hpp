@@ -52,6 +52,11 @@ cl_status cl_key_gather(cl_ctx* ctx, const uint64_t* d_kmers, uint64_t n, uint32
 // graph.hip: reference reads before each read of a chunk (the first half of cl_index_entries_of on its own)
 cl_status cl_ref_bounds(cl_ctx* ctx, const uint8_t* d_accept, uint32_t n, uint32_t ref_base, uint32_t* d_bounds, uint32_t* n_accepted);
 
+// expand.hip: cl_es_verify with the first differing base of the first bad read (~0u: its length or tuple count differs); es_bytes: the
+// tuple bytes, for the achieved bytes/s of timed runs (0: not known)
+cl_status cl_es_verify_at(cl_ctx* ctx, const cl_reads* reads, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, const uint32_t* d_es_ntuples,
+                          uint64_t es_bytes, uint64_t* n_bad, uint32_t* first_bad, uint32_t* first_diff);
+
 // the DNA coder's state-independent half ahead of time (dna.hip): lookahead.hip walks the NEXT chunk's tuples from the hook that
 // cl_dna_encode calls before it waits for its last interval coding
 #include <functional>

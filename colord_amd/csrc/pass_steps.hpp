@@ -101,6 +101,18 @@ inline cl_status append_index_entries(cl_ctx* ctx, const cl_kmer_lists* lists, c
 // here as soon as they have served) a5 candidates among the reference reads before each read (d_bounds), a8/a9 anchors, a10-a12 edit
 // scripts -> tuple streams.  Reads only state that is complete (index, reference reads), so batches are independent here.
 struct TupleStreams { DevBuf<uint8_t> es; DevBuf<uint64_t> es_off; DevBuf<uint32_t> es_nt; uint64_t es_bytes = 0, n_anchors = 0; };
+// cl_ctx_set_verify: every read of the batch rebuilt on the device from its edit script and the reference reads (expand.hip, the inverse
+// of a10-a12) and compared with the input, before anything is coded from the streams.  The entropy-coded bytes are not covered.
+inline cl_status verify_streams(cl_ctx* ctx, const cl_reads* reads, const cl_reads* refs, const TupleStreams& ts)
+{
+	uint64_t n_bad = 0; uint32_t first_bad = 0, first_diff = 0;
+	CL_TRY(cl_es_verify_at(ctx, reads, refs, ts.es.p, ts.es_off.p, ts.es_nt.p, ts.es_bytes, &n_bad, &first_bad, &first_diff));
+	if (n_bad)
+		return cl_fail(ctx, CL_E_MISMATCH, "edit-script check: " + std::to_string(n_bad) + " of " + std::to_string(reads->n_reads) + " reads are not rebuilt from their edit scripts; first: read " +
+			std::to_string(first_bad) + " of the chunk, " + (first_diff == 0xffffffffu ? std::string("its length or tuple count differs") : "first differing base " + std::to_string(first_diff)));
+	ctx->verified_reads += reads->n_reads; ctx->verified_bases += reads->total_bases;
+	return CL_OK;
+}
 inline cl_status tuple_streams(cl_ctx* ctx, const cl_compress_params* P, Handle<cl_kmer_lists, cl_kmer_lists_free>& lists, const cl_index* index, const cl_reads* refs,
                                const cl_reads* reads, const uint32_t* d_bounds, const uint32_t* h_pack_bounds, uint32_t n_packs, TupleStreams& out)
 {
@@ -133,7 +145,8 @@ inline cl_status tuple_streams(cl_ctx* ctx, const cl_compress_params* P, Handle<
 	crefs.release(); cnt.release(); common_off.release(); common.release();
 	const uint64_t es_cap = reads->total_bases + 16ull * n + 4096;
 	DEV_ALLOC(ctx, out.es, es_cap); DEV_ALLOC(ctx, out.es_off, (uint64_t)n + 1); DEV_ALLOC(ctx, out.es_nt, n);
-	return cl_encode_reads(ctx, reads, refs, anc, cc, P->anchor_len, P->min_part_alt, max_rec, P->cost_mult, h_pack_bounds, n_packs, out.es.p, es_cap, out.es_off.p, out.es_nt.p, &out.es_bytes);
+	CL_TRY(cl_encode_reads(ctx, reads, refs, anc, cc, P->anchor_len, P->min_part_alt, max_rec, P->cost_mult, h_pack_bounds, n_packs, out.es.p, es_cap, out.es_off.p, out.es_nt.p, &out.es_bytes));
+	return ctx->verify ? verify_streams(ctx, reads, refs, out) : CL_OK;
 }
 
 // The coder tail of a batch: a14 + a16 the DNA stream, a13 + a15 the quality stream.  The quality stream of level 1 does not depend on

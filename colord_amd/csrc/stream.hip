@@ -390,6 +390,11 @@ extern "C" cl_status cl_compressor_encode(cl_compressor* c, const cl_reads* read
 	return coder.code(c->refs, *job);
 }
 
+extern "C" cl_status cl_compressor_verified(const cl_compressor* c, uint64_t* reads, uint64_t* bases)
+{
+	return c ? cl_ctx_verified(c->ctx, reads, bases) : CL_E_INVALID;
+}
+
 extern "C" cl_status cl_compressor_info(const cl_compressor* c, cl_kmer_stats* stats, uint64_t* first_read, uint64_t* n_reads_total, uint64_t* mean_read_len,
                                         uint32_t* sparse_range, uint32_t* n_refs_total)
 {

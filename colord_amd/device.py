@@ -50,7 +50,8 @@ class _OrderedLib:
     round 4 (`cl_reads_pack: offsets not monotone` once in seven runs of test_chunked_equals_one_call_200_mbases; reproduced at will under
     COLORD_HIP_SYNC_DEBUG, which shifts the timing): a race of the HARNESS, not of the library's pool.  Waiting on an idle stream costs
     microseconds; a host that embeds the library orders its own streams."""
-    _HOST_ONLY = ("cl_last_error", "cl_ctx_kernel_times", "cl_ctx_last_kernel_ms", "cl_ctx_set_timing", "cl_ref_accept")
+    _HOST_ONLY = ("cl_last_error", "cl_ctx_kernel_times", "cl_ctx_last_kernel_ms", "cl_ctx_set_timing", "cl_ref_accept", "cl_ctx_set_verify", "cl_ctx_verified",
+                  "cl_compressor_verified")
 
     def __init__(self, lib, device):
         self._lib, self._device, self._cache = lib, device, {}
@@ -108,6 +109,17 @@ class Context:
             f = line.split("\t")
             out[f[0]] = (float(f[1]), int(f[2]), float(f[3]), float(f[4]) if len(f) > 4 else 0.0)
         return out
+
+    def set_verify(self, on: bool = True):
+        """cl_ctx_set_verify: compress_shard() and compressors of this context rebuild every read from its edit script and compare it
+        with the input (ColordHipError with status CL_E_MISMATCH names the first read that differs)."""
+        self.lib.cl_ctx_set_verify(self.h, int(bool(on)))
+
+    def verified(self):
+        """(reads, bases) checked so far on this context and the encode lanes of its compressor."""
+        r, b = C.c_uint64(0), C.c_uint64(0)
+        _check(None, self.lib.cl_ctx_verified(self.h, C.byref(r), C.byref(b)))
+        return r.value, b.value
 
     # ---- arena ----
     def pack_reads(self, codes: torch.Tensor, offsets: torch.Tensor, ascii: bool = False) -> "Reads":
@@ -297,6 +309,34 @@ class Context:
         _check(self, self.lib.cl_es_flags(self.h, reads.h, es.contiguous().data_ptr() if es.numel() else None, es_off.contiguous().data_ptr(),
                                           base_off.contiguous().data_ptr(), flags.data_ptr()))
         return flags[:int(reads.total_bases)]
+
+    # ---- the inverse of a10-a12 ----
+    def es_expand(self, refs: "Reads", es: torch.Tensor, es_off: torch.Tensor, es_ntuples: torch.Tensor | None = None):
+        """cl_es_expand: the reads their tuple streams describe against `refs`.  Returns (base codes 0..4, offsets [n+1])."""
+        es, es_off = es.contiguous(), es_off.contiguous()
+        n = es_off.numel() - 1
+        nt = es_ntuples.contiguous() if es_ntuples is not None else None
+        off = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        need, codes, cap = C.c_uint64(0), None, 0
+        for _ in range(2):
+            st = self.lib.cl_es_expand(self.h, refs.h, es.data_ptr() if es.numel() else None, es_off.data_ptr(), nt.data_ptr() if nt is not None else None, n,
+                                       codes.data_ptr() if codes is not None else None, cap, off.data_ptr(), C.byref(need))
+            if st == N.CL_E_CAPACITY and need.value > cap:
+                cap = need.value
+                codes = torch.empty(cap, dtype=torch.uint8, device=self.device)
+                continue
+            _check(self, st)
+            break
+        return (codes[:need.value] if codes is not None else torch.empty(0, dtype=torch.uint8, device=self.device)), off
+
+    def es_verify(self, reads: "Reads", refs: "Reads", es: torch.Tensor, es_off: torch.Tensor, es_ntuples: torch.Tensor | None = None):
+        """cl_es_verify: (number of reads of `reads` that their tuple streams do not rebuild, the first of them or None)."""
+        es, es_off = es.contiguous(), es_off.contiguous()
+        nt = es_ntuples.contiguous() if es_ntuples is not None else None
+        n_bad, first = C.c_uint64(0), C.c_uint32(0)
+        _check(self, self.lib.cl_es_verify(self.h, reads.h, refs.h, es.data_ptr() if es.numel() else None, es_off.data_ptr(), nt.data_ptr() if nt is not None else None,
+                                           C.byref(n_bad), C.byref(first)))
+        return n_bad.value, (first.value if n_bad.value else None)
 
     def estimator_logs(self, count: torch.Tensor, total: torch.Tensor) -> torch.Tensor:
         """The decision logarithm -log2(count * (1/total)) as the encoder's kernels evaluate it (calc_logs, utils.h:800-810)."""
@@ -492,6 +532,12 @@ class Compressor(_Obj):
         _check(self.ctx, self.ctx.lib.cl_compressor_info(self.h, C.byref(st), C.byref(a), C.byref(b), C.byref(m), C.byref(r), C.byref(nr)))
         return dict(tot_kmers=st.tot_kmers, n_unique_counted=st.n_unique_counted, first_read=a.value, n_reads_total=b.value, mean_read_len=m.value,
                     sparse_range=r.value, n_refs_total=nr.value)
+
+    def verified(self):
+        """cl_compressor_verified: (reads, bases) rebuilt from their edit scripts and compared with the input (Context.set_verify)."""
+        r, b = C.c_uint64(0), C.c_uint64(0)
+        _check(None, self.ctx.lib.cl_compressor_verified(self.h, C.byref(r), C.byref(b)))
+        return r.value, b.value
 
     def genome_add(self, sequences: "Reads"):
         _check(self.ctx, self.ctx.lib.cl_compressor_genome_add(self.h, sequences.h))

@@ -34,7 +34,8 @@ enum {
 	CL_E_HIP = -2,          /* HIP runtime error (text in cl_last_error) */
 	CL_E_CAPACITY = -3,     /* caller buffer too small; the needed element count was returned */
 	CL_E_NOMEM = -4,
-	CL_E_UNSUPPORTED = -5
+	CL_E_UNSUPPORTED = -5,
+	CL_E_MISMATCH = -6      /* cl_ctx_set_verify: a read is not rebuilt from its edit script (text names the read and the base) */
 };
 
 typedef struct cl_ctx cl_ctx;
@@ -57,6 +58,14 @@ cl_status cl_ctx_last_kernel_ms(const cl_ctx* ctx, const char* kernel, double* m
 cl_status cl_ctx_kernel_times(cl_ctx* ctx, char* buf, uint64_t cap, uint64_t* needed);
 /* Enable/disable per-kernel HIP-event timing (off by default; on adds event records around kernels). */
 void cl_ctx_set_timing(cl_ctx* ctx, int on);
+/* Opt-in check of the edit scripts (off by default; with it off nothing below is launched and every output byte is the same).
+ * While it is on, cl_compress_shard on this context and a cl_compressor created on it (which hands the flag to its encode lanes)
+ * rebuild every read of every chunk on the device from its own edit script and the reference reads (cl_es_verify) right after
+ * cl_encode_reads, and compare it with the input, before the streams are coded: a read that differs makes the call return
+ * CL_E_MISMATCH, the text naming the chunk-relative read and its first differing base.  The entropy-coded bytes are not decoded.
+ * cl_ctx_verified: reads and bases checked so far on this context and its compressor's lanes. */
+void cl_ctx_set_verify(cl_ctx* ctx, int on);
+cl_status cl_ctx_verified(const cl_ctx* ctx, uint64_t* reads, uint64_t* bases);
 
 /* ---- read arena: replaces read_t / read_pack_t (src/colord/utils.h:366-376, in_reads.cpp:24-42) -- */
 /* d_codes: concatenated bases, 1 byte per base; either codes 0..4 (ascii=0) or ASCII ACGTN, upper
@@ -245,6 +254,22 @@ cl_status cl_estimator_logs(cl_ctx* ctx, const uint32_t* d_count, const uint32_t
  * d_base_off: n_reads+1 offsets of the reads' bases (the d_qual_off of cl_qual_encode); d_flags: total_bases bytes. */
 cl_status cl_es_flags(cl_ctx* ctx, const cl_reads* reads, const uint8_t* d_es, const uint64_t* d_es_off, const uint64_t* d_base_off, uint8_t* d_flags);
 
+/* ---- the inverse of a10-a12: a read from its tuple stream, as CDNACoder::Decode applies the tuples it decoded
+ *      (dna_coder.cpp:234-437) to what CEncoder::Encode wrote (encoder.cpp:1672-1691) — on the device, a wave per read ---------- */
+/* The reads that the tuple streams d_es / d_es_off (n_reads + 1 byte offsets) describe against the reference arena `refs`: base
+ * codes 0..4, one byte per base, back to back in d_codes (capacity cap) — the input form of cl_reads_pack with ascii = 0 — and
+ * their n_reads + 1 offsets in d_base_off; *n_out = bases (CL_E_CAPACITY with the size needed if > cap; the offsets are valid then).
+ * d_es_ntuples (optional): the tuple counts the streams must have.  A malformed stream (unknown or truncated tuple, id or position
+ * outside the references, more than 64 alternatives, other tuple count) is CL_E_INVALID, the text naming the first such read; it
+ * never makes the kernels read or write out of range. */
+cl_status cl_es_expand(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, const uint32_t* d_es_ntuples, uint32_t n_reads,
+                       uint8_t* d_codes, uint64_t cap, uint64_t* d_base_off, uint64_t* n_out);
+/* The same walk compared with the arena `reads` the streams were made from instead of stored (nothing is written but the counts):
+ * *n_bad = reads whose length, tuple count or any base (N included) differs, *first_bad = the first of them (~0u: none).  CL_OK
+ * with the counts; a malformed stream is CL_E_INVALID as above. */
+cl_status cl_es_verify(cl_ctx* ctx, const cl_reads* reads, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, const uint32_t* d_es_ntuples,
+                       uint64_t* n_bad, uint32_t* first_bad);
+
 /* ---- a14 + a16: CDNACoder / CEntrComprReads (dna_coder.{h,cpp}, entr_read.h:56-80) --------------------- */
 typedef struct cl_dna_coder cl_dna_coder;
 /* CDNACoder::Init(true, maxCandidates, level, ., n_ref_genome_pseudo_reads): one adaptive model set that
@@ -385,6 +410,8 @@ cl_status cl_compressor_prepare_parts(cl_compressor* c, const cl_reads* chunk, c
  * first_read = global index of this rank's first read (start of its model domain) */
 cl_status cl_compressor_info(const cl_compressor* c, cl_kmer_stats* stats, uint64_t* first_read, uint64_t* n_reads_total, uint64_t* mean_read_len,
                              uint32_t* sparse_range, uint32_t* n_refs_total);
+/* cl_ctx_verified of the compressor's context: the reads and bases its encode calls and lanes have checked (cl_ctx_set_verify) */
+cl_status cl_compressor_verified(const cl_compressor* c, uint64_t* reads, uint64_t* bases);
 
 /* ---- a17, the inverse path: CRangeDecoder (sub_rc.h:216-392), CDNACoder::Decode (dna_coder.cpp:234-437), CQualityCoder::Decode
  *      (quality_coder.cpp:605-657, quality_coder_impl.cpp:506-559,800-849), CIDCoder::Decode (id_coder.cpp:396-600); drivers
