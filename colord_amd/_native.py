@@ -66,6 +66,9 @@ _SIG = {
     "cl_ctx_set_timing": (None, [_P, C.c_int]),
     "cl_ctx_set_verify": (None, [_P, C.c_int]),
     "cl_ctx_verified": (C.c_int32, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cl_ctx_set_verify_streams": (None, [_P, C.c_int]),
+    "cl_ctx_verified_streams": (C.c_int32, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cl_compressor_verified_streams": (C.c_int32, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cl_es_expand": (C.c_int32, [_P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
     "cl_es_verify": (C.c_int32, [_P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "cl_compressor_verified": (C.c_int32, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -135,6 +135,15 @@ extern "C" cl_status cl_ctx_verified(const cl_ctx* c, uint64_t* reads, uint64_t*
 	if (bases) *bases = b;
 	return CL_OK;
 }
+extern "C" void cl_ctx_set_verify_streams(cl_ctx* c, int on) { if (c) c->verify_streams = on != 0; }
+extern "C" cl_status cl_ctx_verified_streams(const cl_ctx* c, uint64_t* parts, uint64_t* symbols, uint64_t* bytes)
+{
+	if (!c) return CL_E_INVALID;
+	if (parts) *parts = c->verified_stream_parts.load();
+	if (symbols) *symbols = c->verified_stream_symbols.load();
+	if (bytes) *bytes = c->verified_stream_bytes.load();
+	return CL_OK;
+}
 extern "C" cl_status cl_ctx_last_kernel_ms(const cl_ctx* c, const char* kernel, double* ms, uint32_t* launches)
 {
 	if (!c || !kernel) return CL_E_INVALID;

@@ -197,6 +197,7 @@ int run_compress(int argc, char** argv)
 	const bool with_qual = R.fastq;
 	cl_compressor* cmp = nullptr;
 	if (O.verify_scripts) cl_ctx_set_verify(ctx, 1);
+	if (O.verify_streams) cl_ctx_set_verify_streams(ctx, 1);
 	ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, nullptr, estimated_bases(R), &cmp), "cl_compressor_create");
 	GenomeMode GM;
 	if (!O.genome.empty()) { GM.read(O); GM.count_kmers(ctx, cmp); }

@@ -10,16 +10,19 @@
 #include <mutex>
 
 inline void ck(cl_ctx* ctx, cl_status s, const char* what) { if (s != CL_OK) die(std::string(what) + ": " + (ctx ? cl_last_error(ctx) : "error")); }
-// a failed encode call of pass 2 (--verify-scripts: a read that its edit script does not rebuild): what is on disk is half a file and goes with the message
+// a failed encode call of pass 2 (--verify-scripts: a read that its edit script does not rebuild; --verify-streams: a coded part that does not decode): what is on disk is half a file and goes with the message
 inline void ck_encode(cl_ctx* ctx, cl_status s, const std::string& out_path)
 {
 	if (s == CL_OK) return;
 	(void)remove(out_path.c_str());
 	die(std::string("pass 2: ") + cl_last_error(ctx) + " (no archive was written)");
 }
-// -v with --verify-scripts: what the compressor's contexts checked
+// -v with --verify-scripts / --verify-streams: what the compressor's contexts checked
 inline void verified_line(const Options& O, cl_compressor* cmp, const char* who = "")
 {
+	uint64_t p = 0, s = 0, n = 0;
+	if (O.verify_streams && O.verbose && cl_compressor_verified_streams(cmp, &p, &s, &n) == CL_OK)
+		fprintf(stderr, "# coded streams verified%s: %llu parts, %llu symbols, %llu bytes decode to the models' intervals\n", who, (unsigned long long)p, (unsigned long long)s, (unsigned long long)n);
 	if (!O.verify_scripts || !O.verbose) return;
 	uint64_t r = 0, b = 0;
 	if (cl_compressor_verified(cmp, &r, &b) == CL_OK) fprintf(stderr, "# edit scripts verified%s: %llu reads, %llu bases rebuilt on the device and equal to the input\n", who, (unsigned long long)r, (unsigned long long)b);

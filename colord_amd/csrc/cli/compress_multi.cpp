@@ -108,6 +108,7 @@ int run_compress_multi(const Options& O)
 		cl_exchange X; if (T) X = T->exchange();
 		cl_compressor* cmp = nullptr;
 		if (O.verify_scripts) cl_ctx_set_verify(ctx, 1);
+		if (O.verify_streams) cl_ctx_set_verify_streams(ctx, 1);
 		ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, T ? &X : nullptr, my_bases, &cmp), "cl_compressor_create");
 		if (GM.on) GM.count_kmers(ctx, cmp);
 		// chunks of whole reader packs (the packs are cut from this rank's first read on: in_reads.cpp:62-77).  The chunk size follows the

@@ -36,6 +36,7 @@ struct Options {
 	bool stream_input = false;                      // --stream-input: the input is read three times (k-mers, reference reads, coding) and only a window of chunks is resident in HBM
 	int domains = 1;                                // --domains K: K INDEPENDENT model domains on one GPU (own k-mer set, references, index, models each): decoded side by side
 	bool verify_scripts = false;                    // --verify-scripts: cl_ctx_set_verify on every compressor's context
+	bool verify_streams = false;                    // --verify-streams: cl_ctx_set_verify_streams on every compressor's context
 	int gpus = 1; std::vector<int> gpu_list; std::string transport = "rccl";   // --gpus N [--gpu-list a,b,..] [--transport rccl|host]: reads sharded over N GPUs (run_compress_multi)
 	Preset P{}; QDef qd;                            // resolved by parse_options: the preset of source and priority with the options laid over it, the quality thresholds / representatives
 	int argc = 0; char** argv = nullptr;            // the command line as given (`info` stream)
@@ -60,6 +61,9 @@ inline void usage()
 		"                     four chunks is resident at a time instead of the whole input (same archive)\n"
 		"  --verify-scripts   every read is rebuilt on the device from its edit script and the reference reads and compared with the input; the entropy-coded bytes are not decoded\n"
 		"                     (a read that differs: message, no archive, non-zero exit)\n"
+		"  --verify-streams   each coded part of the dna and qual streams is decoded on the device with the decoder's interval arithmetic: every symbol must fall in the interval\n"
+		"                     its model gave it and the part must end at its size; the models themselves are not replayed (edit scripts -> sort keys -> triples is not covered)\n"
+		"                     (a part that does not decode: message, no archive, non-zero exit)\n"
 		"  --domains K        K independent model domains (equal shares of the reads, each compressed on its own): `colord_hip decompress`\n"
 		"                     decodes them side by side; costs archive size (own k-mer statistics and reference reads per domain)\n"
 		"  --gpus N [--gpu-list a,b,..] [--transport rccl|host]   reads sharded over N GPUs, one host thread and one model domain per GPU;\n"
@@ -115,6 +119,7 @@ inline Options parse_options(int argc, char** argv)
 		else if (a == "--part-symbols") { O.part_symbols = strtoull(need(i).c_str(), nullptr, 10); if (O.part_symbols < 1024 || O.part_symbols > (2u << 21)) die("--part-symbols must be in [1024, 4194304]"); }
 		else if (a == "--stream-input") O.stream_input = true;
 		else if (a == "--verify-scripts") O.verify_scripts = true;
+		else if (a == "--verify-streams") O.verify_streams = true;
 		else if (a == "--parse-threads") { O.parse_threads = atoi(need(i).c_str()); if (O.parse_threads < 1 || O.parse_threads > 256) die("--parse-threads must be in [1, 256]"); }
 		else if (a == "-h" || a == "--help") { usage(); exit(0); }
 		else if (!a.empty() && a[0] == '-' && a.size() > 1) die("unknown option " + a);

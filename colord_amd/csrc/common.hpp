@@ -344,6 +344,8 @@ struct cl_ctx {
 	bool timing = false;
 	bool verify = false;                         // cl_ctx_set_verify: tuple_streams (pass_steps.hpp) rebuilds every read from its edit script and compares it with the input
 	std::atomic<uint64_t> verified_reads{ 0 }, verified_bases{ 0 };   // what this context has checked so (cl_ctx_verified adds the encode lanes')
+	bool verify_streams = false;                 // cl_ctx_set_verify_streams: the DNA and quality coders run every coded part through the decoder's interval arithmetic (rc_check.hpp)
+	std::atomic<uint64_t> verified_stream_parts{ 0 }, verified_stream_symbols{ 0 }, verified_stream_bytes{ 0 };   // what the coders on this context have checked so
 	std::map<std::string, KernelTime> times;     // per-kernel accumulated HIP-event time of the last API call
 	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
 	std::vector<double> pending_bytes, pending_cells;

@@ -11,6 +11,7 @@
 #include <functional>
 #include "objects.hpp"
 #include "rc_dev.hpp"
+#include "rc_check.hpp"    // the opt-in check of the coded parts (cl_ctx_set_verify_streams)
 #include "es_format.hpp"      // tuple types and EsReader, shared with expand.hip
 #include <algorithm>
 #include <deque>
@@ -1022,7 +1023,7 @@ namespace {
 struct SideSync { hipStream_t s = nullptr; ~SideSync() { if (s) (void)hipStreamSynchronize(s); } };
 struct PendingGroup {
 	DevBuf<triple_t> trip; DevBuf<uint64_t> d_gbase, d_out_off, d_size, d_dst_off; DevBuf<uint32_t> d_plen; DevBuf<uint8_t> tmp;
-	std::vector<uint64_t> out_off; std::vector<uint32_t> rank; uint32_t p0 = 0, np = 0;   // rank: part -> place (descending length)
+	std::vector<uint64_t> out_off; std::vector<uint32_t> rank; uint32_t p0 = 0, np = 0; uint64_t n_syms = 0;   // rank: part -> place (descending length)
 	hipStream_t stream = nullptr;                   // where its interval coder runs
 	SideSync sync;                                  // destroyed first: nothing above is released while the side stream runs
 };
@@ -1337,7 +1338,7 @@ cl_status dna_evolve_batch(cl_ctx* ctx, cl_dna_coder* D, const cl_reads* refs, c
 		const uint32_t p1 = GP->p1, np = p1 - p0, ng = (np + 63) / 64;
 		const uint64_t s0 = GP->s0, n_syms = GP->n_syms;
 		const std::vector<uint32_t>& rank = GP->rank; const std::vector<uint32_t>& plen_r = GP->plen_r;
-		auto G = std::make_unique<PendingGroup>(); G->p0 = p0; G->np = np; G->rank = rank;
+		auto G = std::make_unique<PendingGroup>(); G->p0 = p0; G->np = np; G->rank = rank; G->n_syms = GP->n_syms;
 		G->d_gbase = std::move(GP->d_gbase); G->d_plen = std::move(GP->d_plen);
 		DevBuf<uint64_t>& d_gbase = G->d_gbase; DevBuf<uint32_t>& d_plen = G->d_plen; DevBuf<triple_t>& trip = G->trip;
 		DEV_ALLOC(ctx, trip, GP->trip_words);
@@ -1477,7 +1478,10 @@ extern "C" cl_status cl_dna_encode(cl_ctx* ctx, cl_dna_coder* D, const cl_reads*
 		HIP_TRY(ctx, hipMemcpyAsync(g.d_dst_off.p, dst_off.data(), g.np * 8, hipMemcpyHostToDevice, ctx->stream));
 		LAUNCH(ctx, k_gather_bytes2, g.np, 256, (const uint8_t*)g.tmp.p, (const uint64_t*)g.d_out_off.p, (const uint64_t*)g.d_dst_off.p, (const uint64_t*)g.d_size.p, d_out);
 		HIP_TRY(ctx, hipGetLastError());
+		RcCheckRun check;                                                        // cl_ctx_set_verify_streams: the final bytes through the decoder's arithmetic (rc_check.hpp)
+		if (ctx->verify_streams) CL_TRY(rc_check_launch(ctx, check, g.trip.p, g.d_gbase.p, g.d_plen.p, g.np, g.n_syms, d_out, w, w - written, g.d_dst_off.p, g.d_size.p));
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                         // (dst_off is read by the copy above)
+		if (ctx->verify_streams) CL_TRY(rc_check_collect(ctx, check, "dna", g.trip.p, g.d_gbase.p, g.d_plen.p, d_out, dst_off, g.rank, g.p0, h_part_sizes + g.p0));
 		written = w;
 		return CL_OK;
 	};

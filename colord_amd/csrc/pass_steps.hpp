@@ -165,6 +165,7 @@ struct ChunkCoder {
 	~ChunkCoder() { if (qthread.joinable()) qthread.join(); }
 	cl_status quality_on(cl_ctx* on, const uint8_t* d_flags)
 	{
+		if (on != ctx) on->verify_streams = ctx->verify_streams;      // (the quality coder's own context checks its parts when the caller's does)
 		return cl_qual_encode(on, qual, io.reads, io.d_quals, io.d_base_off, d_flags, io.h_part_bounds, io.n_parts, io.d_qual_out, io.qual_cap, io.h_qual_part_sizes, &io.info->qual_bytes);
 	}
 	void start_quality() { if (overlap) qthread = std::thread([this]() { qstatus = quality_on(qctx, nullptr); }); }

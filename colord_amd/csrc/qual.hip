@@ -19,6 +19,7 @@
 #include <chrono>
 #include "objects.hpp"
 #include "rc_dev.hpp"
+#include "rc_check.hpp"    // the opt-in check of the coded parts (cl_ctx_set_verify_streams)
 #include <algorithm>
 
 namespace {
@@ -743,7 +744,10 @@ extern "C" cl_status cl_qual_encode(cl_ctx* ctx, cl_qual_coder* Q, const cl_read
 		HIP_TRY(ctx, hipMemcpyAsync(PG.d_dst_off.p, dst_off.data(), np * 8, hipMemcpyHostToDevice, ctx->stream));
 		LAUNCH(ctx, k_gather_bytes, np, 256, (const uint8_t*)PG.tmp.p, (const uint64_t*)PG.d_out_off.p, (const uint64_t*)PG.d_dst_off.p, (const uint64_t*)PG.d_size.p, d_out);
 		HIP_TRY(ctx, hipGetLastError());
+		RcCheckRun check;                                                       // cl_ctx_set_verify_streams: the final bytes through the decoder's arithmetic (rc_check.hpp)
+		if (ctx->verify_streams) CL_TRY(rc_check_launch(ctx, check, PG.trip.p, PG.d_gbase.p, PG.d_plen.p, np, PG.n_syms, d_out, w, w - written, PG.d_dst_off.p, PG.d_size.p));
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		if (ctx->verify_streams) CL_TRY(rc_check_collect(ctx, check, "qual", PG.trip.p, PG.d_gbase.p, PG.d_plen.p, d_out, dst_off, PG.rank, p0, h_part_sizes + p0));
 		written = w;
 		Q->symbols_coded += PG.n_syms;
 	}

@@ -395,6 +395,25 @@ extern "C" cl_status cl_compressor_verified(const cl_compressor* c, uint64_t* re
 	return c ? cl_ctx_verified(c->ctx, reads, bases) : CL_E_INVALID;
 }
 
+// every context that codes for the compressor: its own (the DNA stream; the quality stream of levels 2 and 3) and the quality coder's
+extern "C" cl_status cl_compressor_verified_streams(const cl_compressor* c, uint64_t* parts, uint64_t* symbols, uint64_t* bytes)
+{
+	if (!c) return CL_E_INVALID;
+	uint64_t v[3] = { 0, 0, 0 };
+	CL_TRY(cl_ctx_verified_streams(c->ctx, &v[0], &v[1], &v[2]));
+	const cl_ctx* qc = c->qual ? cl_qual_coder_ctx(c->qual) : nullptr;
+	if (qc && qc != c->ctx)
+	{
+		uint64_t q[3] = { 0, 0, 0 };
+		CL_TRY(cl_ctx_verified_streams(qc, &q[0], &q[1], &q[2]));
+		for (int i = 0; i < 3; ++i) v[i] += q[i];
+	}
+	if (parts) *parts = v[0];
+	if (symbols) *symbols = v[1];
+	if (bytes) *bytes = v[2];
+	return CL_OK;
+}
+
 extern "C" cl_status cl_compressor_info(const cl_compressor* c, cl_kmer_stats* stats, uint64_t* first_read, uint64_t* n_reads_total, uint64_t* mean_read_len,
                                         uint32_t* sparse_range, uint32_t* n_refs_total)
 {

@@ -51,7 +51,7 @@ class _OrderedLib:
     COLORD_HIP_SYNC_DEBUG, which shifts the timing): a race of the HARNESS, not of the library's pool.  Waiting on an idle stream costs
     microseconds; a host that embeds the library orders its own streams."""
     _HOST_ONLY = ("cl_last_error", "cl_ctx_kernel_times", "cl_ctx_last_kernel_ms", "cl_ctx_set_timing", "cl_ref_accept", "cl_ctx_set_verify", "cl_ctx_verified",
-                  "cl_compressor_verified")
+                  "cl_compressor_verified", "cl_ctx_set_verify_streams", "cl_ctx_verified_streams", "cl_compressor_verified_streams")
 
     def __init__(self, lib, device):
         self._lib, self._device, self._cache = lib, device, {}
@@ -120,6 +120,18 @@ class Context:
         r, b = C.c_uint64(0), C.c_uint64(0)
         _check(None, self.lib.cl_ctx_verified(self.h, C.byref(r), C.byref(b)))
         return r.value, b.value
+
+    def set_verify_streams(self, on: bool = True):
+        """cl_ctx_set_verify_streams: the DNA and quality coders of this context decode every coded part on the device against the
+        intervals its models gave (ColordHipError with status CL_E_MISMATCH names the stream, the part and the symbol).  The models
+        themselves are not replayed."""
+        self.lib.cl_ctx_set_verify_streams(self.h, int(bool(on)))
+
+    def verified_streams(self):
+        """(parts, symbols, bytes) of the coded streams checked so far by the coders on this context."""
+        p, s, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(None, self.lib.cl_ctx_verified_streams(self.h, C.byref(p), C.byref(s), C.byref(b)))
+        return p.value, s.value, b.value
 
     # ---- arena ----
     def pack_reads(self, codes: torch.Tensor, offsets: torch.Tensor, ascii: bool = False) -> "Reads":
@@ -538,6 +550,13 @@ class Compressor(_Obj):
         r, b = C.c_uint64(0), C.c_uint64(0)
         _check(None, self.ctx.lib.cl_compressor_verified(self.h, C.byref(r), C.byref(b)))
         return r.value, b.value
+
+    def verified_streams(self):
+        """cl_compressor_verified_streams: (parts, symbols, bytes) of the dna and qual streams decoded against their models' intervals
+        (Context.set_verify_streams), over the compressor's context and its quality coder's."""
+        p, s, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(None, self.ctx.lib.cl_compressor_verified_streams(self.h, C.byref(p), C.byref(s), C.byref(b)))
+        return p.value, s.value, b.value
 
     def genome_add(self, sequences: "Reads"):
         _check(self.ctx, self.ctx.lib.cl_compressor_genome_add(self.h, sequences.h))

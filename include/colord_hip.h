@@ -35,7 +35,9 @@ enum {
 	CL_E_CAPACITY = -3,     /* caller buffer too small; the needed element count was returned */
 	CL_E_NOMEM = -4,
 	CL_E_UNSUPPORTED = -5,
-	CL_E_MISMATCH = -6      /* cl_ctx_set_verify: a read is not rebuilt from its edit script (text names the read and the base) */
+	CL_E_MISMATCH = -6      /* cl_ctx_set_verify: a read is not rebuilt from its edit script (text names the read and the base);
+	                         * cl_ctx_set_verify_streams: a coded part does not decode to its models' intervals or does not end at its
+	                         * size (text names the stream, the part, its symbols and bytes, and the first such symbol or the byte counts) */
 };
 
 typedef struct cl_ctx cl_ctx;
@@ -66,6 +68,20 @@ void cl_ctx_set_timing(cl_ctx* ctx, int on);
  * cl_ctx_verified: reads and bases checked so far on this context and its compressor's lanes. */
 void cl_ctx_set_verify(cl_ctx* ctx, int on);
 cl_status cl_ctx_verified(const cl_ctx* ctx, uint64_t* reads, uint64_t* bases);
+/* Opt-in check of the entropy-coded bytes (off by default; with it off nothing below is launched or allocated and every output byte
+ * is the same).  While it is on, cl_dna_encode and cl_qual_encode on this context (and so cl_compress_shard and a cl_compressor
+ * created on it, which hands the flag to its quality coder's context) run every coded part, in its final place in the caller's
+ * buffer, through the DECODER's interval arithmetic on the device (CRangeDecoder, sub_rc.h:216-392: Start, GetCumulativeFreq,
+ * UpdateFrequency with its renormalisation), one lane per part: every symbol must fall in the interval (cum, freq, total) its model
+ * gave it, and the part must end at its size (8 + the bytes the renormalisation asks for).  A part that does not: CL_E_MISMATCH, the
+ * text naming the stream, the part in call order, its symbols and bytes and the first symbol that does not decode (or the bytes
+ * consumed and stored).  Together with cl_ctx_set_verify: input -> edit scripts and triples -> final bytes are covered.  NOT
+ * covered: edit scripts -> sort keys -> triples — the models themselves are not replayed (walks, sorts, model evolution).  A quality
+ * coder of mode `none` codes nothing and checks nothing.
+ * cl_ctx_verified_streams: parts, symbols and bytes the coders have checked so far ON THIS CONTEXT (a quality coder with a context of
+ * its own counts there; cl_compressor_verified_streams adds them up). */
+void cl_ctx_set_verify_streams(cl_ctx* ctx, int on);
+cl_status cl_ctx_verified_streams(const cl_ctx* ctx, uint64_t* parts, uint64_t* symbols, uint64_t* bytes);
 
 /* ---- read arena: replaces read_t / read_pack_t (src/colord/utils.h:366-376, in_reads.cpp:24-42) -- */
 /* d_codes: concatenated bases, 1 byte per base; either codes 0..4 (ascii=0) or ASCII ACGTN, upper
@@ -412,6 +428,9 @@ cl_status cl_compressor_info(const cl_compressor* c, cl_kmer_stats* stats, uint6
                              uint32_t* sparse_range, uint32_t* n_refs_total);
 /* cl_ctx_verified of the compressor's context: the reads and bases its encode calls and lanes have checked (cl_ctx_set_verify) */
 cl_status cl_compressor_verified(const cl_compressor* c, uint64_t* reads, uint64_t* bases);
+/* cl_ctx_verified_streams summed over the contexts that code for the compressor (its own and its quality coder's): the parts, symbols
+ * and bytes of the dna and qual streams that were decoded against their models' intervals (cl_ctx_set_verify_streams) */
+cl_status cl_compressor_verified_streams(const cl_compressor* c, uint64_t* parts, uint64_t* symbols, uint64_t* bytes);
 
 /* ---- a17, the inverse path: CRangeDecoder (sub_rc.h:216-392), CDNACoder::Decode (dna_coder.cpp:234-437), CQualityCoder::Decode
  *      (quality_coder.cpp:605-657, quality_coder_impl.cpp:506-559,800-849), CIDCoder::Decode (id_coder.cpp:396-600); drivers
