@@ -32,6 +32,14 @@ class KmerStats(C.Structure):
                 ("n_unique_counted", C.c_uint64), ("total_count_filtered", C.c_uint64)]
 
 
+class Digest(C.Structure):
+    """cl_digest: reads and symbols counted, and the 64-bit content sum; digests of disjoint sets of reads add field by field."""
+    _fields_ = [("reads", C.c_uint64), ("symbols", C.c_uint64), ("sum", C.c_uint64)]
+
+    def triple(self):
+        return self.reads, self.symbols, self.sum
+
+
 _P = C.c_void_p
 class CompressParams(C.Structure):
     _fields_ = [("k", C.c_uint32), ("f", C.c_uint32), ("ci", C.c_uint32), ("cs", C.c_uint32), ("c", C.c_uint32),
@@ -69,6 +77,15 @@ _SIG = {
     "cl_ctx_set_verify_streams": (None, [_P, C.c_int]),
     "cl_ctx_verified_streams": (C.c_int32, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cl_compressor_verified_streams": (C.c_int32, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cl_ctx_set_digest": (None, [_P, C.c_int]),
+    "cl_ctx_digest": (C.c_int32, [_P, C.POINTER(Digest), C.POINTER(Digest)]),
+    "cl_compressor_digest": (C.c_int32, [_P, C.POINTER(Digest), C.POINTER(Digest)]),
+    "cl_digest_bases": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(Digest)]),
+    "cl_digest_quals": (C.c_int32, [_P, C.POINTER(QualParams), _P, _P, _P, C.c_uint64, C.POINTER(Digest)]),
+    "cl_digest_bases_host": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(Digest)]),
+    "cl_digest_bytes_host": (C.c_int32, [C.c_uint32, _P, _P, C.c_uint64, C.c_uint64, C.POINTER(Digest)]),
+    "cl_qual_decoder_set_digest": (C.c_int32, [_P, C.c_int, C.c_uint64]),
+    "cl_qual_decoder_digest": (C.c_int32, [_P, C.POINTER(Digest)]),
     "cl_es_expand": (C.c_int32, [_P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
     "cl_es_verify": (C.c_int32, [_P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "cl_compressor_verified": (C.c_int32, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -198,6 +198,7 @@ int run_compress(int argc, char** argv)
 	cl_compressor* cmp = nullptr;
 	if (O.verify_scripts) cl_ctx_set_verify(ctx, 1);
 	if (O.verify_streams) cl_ctx_set_verify_streams(ctx, 1);
+	if (O.digest) cl_ctx_set_digest(ctx, 1);
 	ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, nullptr, estimated_bases(R), &cmp), "cl_compressor_create");
 	GenomeMode GM;
 	if (!O.genome.empty()) { GM.read(O); GM.count_kmers(ctx, cmp); }
@@ -226,7 +227,7 @@ int run_compress(int argc, char** argv)
 		pipe.t_wait, t_check, t_upload, t_scan, R.t_book, R.t_copy, R.threads);
 	const uint32_t n = (uint32_t)R.n_reads; const uint64_t total = R.n_bases;
 	if (!n) die("no reads in " + O.in);
-	HeaderCoder hdr; hdr.start(R, n, O.header_mode);
+	HeaderCoder hdr; hdr.want_digest = O.digest; hdr.start(R, n, O.header_mode);
 	cl_kmer_stats ks{};
 	ck(ctx, cl_compressor_count_finish(cmp, &ks), "k-mer counting");
 	lap("k-mers counted");
@@ -303,6 +304,13 @@ int run_compress(int argc, char** argv)
 	hdr.add_to(ar, s_header);
 	const Totals tot{ n, total, mean_read_len, sparse_range, k, with_qual };
 	add_meta(ar, s_meta, O, GM, tot);
+	if (O.digest)
+	{	// what the compressor's encode calls digested of their chunks, and the ids
+		cl_digest dd{ 0, 0, 0 }, dq{ 0, 0, 0 };
+		ck(ctx, cl_compressor_digest(cmp, &dd, &dq), "cl_compressor_digest");
+		if (dd.reads != n || dd.symbols != total) die("internal: the content digest did not see every read");
+		add_digest(ar, dd, with_qual && O.P.qual_mode != 8 ? &dq : nullptr, hdr.digest);
+	}
 	finish_archive(ar, O, R, tot);
 	gzclose(R.g);
 	lap("archive closed");

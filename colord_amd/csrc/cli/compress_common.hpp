@@ -6,6 +6,7 @@
 #include "options.hpp"
 #include "fastx_input.hpp"
 #include "genome_io.hpp"
+#include "digest_stream.hpp"
 #include <ctime>
 #include <mutex>
 
@@ -208,8 +209,24 @@ inline void announce(cl_ctx* ctx, cl_compressor* cmp, const DevChunk& x)
 // coded on a host thread of its own, next to the GPU path
 struct HeaderCoder {
 	std::vector<std::vector<uint8_t>> parts; std::vector<uint32_t> counts; std::string err; std::thread th;
+	bool want_digest = false; cl_digest digest{ 0, 0, 0 };                   // --digest: the header digest, on this thread too
+	// what `colord_hip decompress` emits for the ids under the archive's -i mode (cl_id_decode_part): org the id and whether the '+' line repeats it,
+	// main nothing, none "@"; FASTA has no '+' line
+	void digest_headers(const Reader& R, uint32_t n, int header_mode)
+	{
+		DigestFeed f;
+		for (uint32_t i = 0; i < n; ++i)
+		{
+			if (header_mode == 0) for (uint64_t j = R.id_off[i]; j < R.id_off[i + 1]; ++j) f.push(R.ids[j]);
+			else if (header_mode == 2) f.push('@');
+			f.push(header_mode == 0 && R.fastq && R.plus[i] ? 1 : 0);
+			f.end_read(DG_HEADER);
+		}
+		digest = f.d;
+	}
 	void code_headers(const Reader& R, uint32_t n, int header_mode)
 	{
+		if (want_digest) digest_headers(R, n, header_mode);
 		cl_id_coder* idc = nullptr;
 		if (cl_id_coder_create(header_mode, &idc) != CL_OK) { err = "cl_id_coder_create"; return; }
 		uint32_t i = 0;
@@ -258,7 +275,7 @@ inline std::vector<uint8_t> pack_meta(const MetaIn& M)
 	return meta;
 }
 // The tail of an archive.  add_meta: the number of reference reads (all, or those the sparse mode accepts), the genome's md5, `meta`;
-// finish_archive: `info` and the footer.  (The drivers add `header`, `ref-genome`, `hipdomains` around them in their archives' order.)
+// finish_archive: `info` and the footer.  (The drivers add `header`, `ref-genome`, `hipdomains`, `hipdigest` around them in their archives' order.)
 struct Totals { uint32_t n_reads; uint64_t n_bases, mean_read_len; uint32_t sparse_range, k; bool with_qual; };
 inline void add_meta(ArchiveWriter& ar, int stream, const Options& O, const GenomeMode& GM, const Totals& T)
 {
@@ -270,6 +287,13 @@ inline void add_meta(ArchiveWriter& ar, int stream, const Options& O, const Geno
 	const std::vector<uint8_t> meta = pack_meta(MetaIn{ T.n_reads, GM.n_pseudo, tot_ref, P.c, P.level, O.source, T.mean_read_len, T.with_qual, P.qual_mode, O.qd.rev, O.header_mode, P.sparse != 0, T.sparse_range, O.exponent,
 	                                                    GM.on, GM.stored, GM.read_len, (T.k - 1) * 10, md });
 	ar.add(stream, meta.data(), meta.size(), 0);
+}
+// --digest: the `hipdigest` stream (digest_stream.hpp), before finish_archive; qual: null without a quality stream or in mode none
+inline void add_digest(ArchiveWriter& ar, const cl_digest& dna, const cl_digest* qual, const cl_digest& header)
+{
+	DigestSet S; S.flags = 1u | (qual ? 2u : 0u) | 4u; S.d[0] = dna; if (qual) S.d[1] = *qual; S.d[2] = header;
+	const std::vector<uint8_t> b = S.pack();
+	ar.add(ar.reg("hipdigest"), b.data(), b.size(), 0);
 }
 inline void finish_archive(ArchiveWriter& ar, const Options& O, const Reader& R, const Totals& T)
 {

@@ -4,7 +4,7 @@
 // bases), cuts its own reader packs and chunks, and drives its own cl_compressor; the two exchanges of the *_finish steps run through the
 // Transport (RCCL, or host staging) bound to cl_exchange; every rank is one model domain of the coders.  Each rank writes ITS parts into the
 // archive file at the offsets an all-gather of the byte counts gives it (pwrite; no part travels to another rank); rank 0's thread adds
-// `meta`, `header`, `hipdomains`, `info` and the footer.  Also `colord_hip rccl-selftest`.
+// `meta`, `header`, `hipdomains`, `hipdigest` (--digest), `info` and the footer.  Also `colord_hip rccl-selftest`.
 #include "compress_common.hpp"
 #include "transport.hpp"
 
@@ -20,6 +20,7 @@ struct RankOut {
 	uint64_t n_reads = 0, mean_read_len = 0; uint32_t sparse_range = 0, n_refs = 0; cl_kmer_stats ks{};
 	uint64_t dna_base = 0, qual_base = 0, qual_framed = 0;     // where its framed `dna` / `qual` parts start in the file; bytes of the latter
 	uint64_t moved = 0;
+	cl_digest dig[2] = { { 0, 0, 0 }, { 0, 0, 0 } }, dig_all[2] = { { 0, 0, 0 }, { 0, 0, 0 } };      // --digest: dna / qual of this rank's reads; of all ranks (as gathered with the byte counts)
 };
 uint32_t varint_len(uint64_t x) { uint32_t n = 1; for (; x; x >>= 8) ++n; return n; }
 }
@@ -77,7 +78,7 @@ int run_compress_multi(const Options& O)
 			while (r < world && (double)acc >= (double)total * r / world) first[r++] = i;
 		}
 	}
-	HeaderCoder hdr; hdr.start(R, (uint32_t)n, O.header_mode);
+	HeaderCoder hdr; hdr.want_digest = O.digest; hdr.start(R, (uint32_t)n, O.header_mode);
 
 	// transports
 	std::vector<std::unique_ptr<Transport>> tp(world);
@@ -109,6 +110,10 @@ int run_compress_multi(const Options& O)
 		cl_compressor* cmp = nullptr;
 		if (O.verify_scripts) cl_ctx_set_verify(ctx, 1);
 		if (O.verify_streams) cl_ctx_set_verify_streams(ctx, 1);
+		// --digest: a rank's compressor knows its first read in the whole input (exchange 1) and digests its chunks as it encodes them; an independent
+		// domain's compressor counts from 0, so its chunks are digested here, at their global read indices, when they first reach the device
+		const bool digest_qual = with_qual && O.P.qual_mode != 8;
+		if (O.digest && !independent) cl_ctx_set_digest(ctx, 1);
 		ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, T ? &X : nullptr, my_bases, &cmp), "cl_compressor_create");
 		if (GM.on) GM.count_kmers(ctx, cmp);
 		// chunks of whole reader packs (the packs are cut from this rank's first read on: in_reads.cpp:62-77).  The chunk size follows the
@@ -136,6 +141,11 @@ int run_compress_multi(const Options& O)
 			fill(c0, i);
 			DevChunk dc = DevChunk::from(host, with_qual);
 			up.upload(ctx, host, dc);
+			if (O.digest && independent)
+			{
+				ck(ctx, cl_digest_bases(ctx, dc.reads, c0, &RO.dig[0]), "content digest");
+				if (digest_qual) ck(ctx, cl_digest_quals(ctx, &prm.qp, dc.reads, dc.d_quals, dc.d_off, c0, &RO.dig[1]), "content digest");
+			}
 			ck(ctx, cl_compressor_count_add(cmp, dc.reads), "pass 1");
 			if (O.stream_input) up.release(dc);                                 // (--stream-input: a chunk leaves HBM after each pass, as in the single-GPU path)
 			cut.push_back(c0);
@@ -186,15 +196,17 @@ int run_compress_multi(const Options& O)
 		(void)hipFree(d_dna); if (d_qual) (void)hipFree(d_qual);
 		up.clear();
 		// where this rank's parts go: an all-gather of the framed byte counts, an exclusive sum, pwrite — `dna` of all ranks first, then `qual`
-		uint64_t mine[2] = { 0, 0 };
+		if (O.digest && !independent) ck(ctx, cl_compressor_digest(cmp, &RO.dig[0], &RO.dig[1]), "cl_compressor_digest");
+		uint64_t mine[8] = { 0, 0, RO.dig[0].reads, RO.dig[0].symbols, RO.dig[0].sum, RO.dig[1].reads, RO.dig[1].symbols, RO.dig[1].sum };      // framed bytes of `dna`, `qual`; the content digests travel with them
 		for (size_t p = 0; p < RO.dsz.size(); ++p) mine[0] += varint_len(RO.counts[p]) + RO.dsz[p];
 		for (size_t p = 0; p < RO.qsz.size(); ++p) mine[1] += varint_len(0) + RO.qsz[p];
 		if (T)
 		{
-			std::vector<uint64_t> all(2 * (size_t)world);
-			ck(ctx, T->all_gather_host(mine, 2, all.data()), "all-gather of the stream sizes");
-			uint64_t dna_all = 0; for (uint32_t r = 0; r < world; ++r) { if (r == rank) RO.dna_base = dna_all; dna_all += all[2 * r]; }
-			uint64_t q = dna_all; for (uint32_t r = 0; r < world; ++r) { if (r == rank) RO.qual_base = q; q += all[2 * r + 1]; }
+			std::vector<uint64_t> all(8 * (size_t)world);
+			ck(ctx, T->all_gather_host(mine, 8, all.data()), "all-gather of the stream sizes");
+			uint64_t dna_all = 0; for (uint32_t r = 0; r < world; ++r) { if (r == rank) RO.dna_base = dna_all; dna_all += all[8 * r]; }
+			uint64_t q = dna_all; for (uint32_t r = 0; r < world; ++r) { if (r == rank) RO.qual_base = q; q += all[8 * r + 1]; }
+			for (uint32_t r = 0; r < world; ++r) for (int s = 0; s < 2; ++s) { RO.dig_all[s].reads += all[8 * r + 2 + 3 * s]; RO.dig_all[s].symbols += all[8 * r + 3 + 3 * s]; RO.dig_all[s].sum += all[8 * r + 4 + 3 * s]; }
 		}
 		else
 		{	// independent domains run one after the other: a domain's parts follow those of the domains before it
@@ -262,6 +274,13 @@ int run_compress_multi(const Options& O)
 	if (first_read != n) die("internal: the ranks' reads do not add up");
 	if (independent) for (uint32_t r = 0; r < world; ++r) le<uint32_t>(dom, out[r].sparse_range);
 	ar.add(s_dom, dom.data(), dom.size(), 0);
+	if (O.digest)
+	{	// the ranks' digests added: as rank 0 gathered them with the byte counts, or (independent domains: nothing is exchanged) from the domains' own
+		cl_digest dd[2] = { out[0].dig_all[0], out[0].dig_all[1] };
+		if (independent) for (int s = 0; s < 2; ++s) { dd[s] = cl_digest{ 0, 0, 0 }; for (uint32_t r = 0; r < world; ++r) { dd[s].reads += out[r].dig[s].reads; dd[s].symbols += out[r].dig[s].symbols; dd[s].sum += out[r].dig[s].sum; } }
+		if (dd[0].reads != n || dd[0].symbols != total) die("internal: the content digest did not see every read");
+		add_digest(ar, dd[0], with_qual && O.P.qual_mode != 8 ? &dd[1] : nullptr, hdr.digest);
+	}
 	finish_archive(ar, O, R, tot);
 	if (use_rccl) rccl.destroy_all();
 	tp.clear();

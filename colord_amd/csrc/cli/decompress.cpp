@@ -1,7 +1,8 @@
-// decompress.cpp — `colord_hip decompress in.colord out.fastq|out.fasta` and `colord_hip info in.colord`: the reference's
+// decompress.cpp — `colord_hip decompress in.colord out.fastq|out.fasta`, `colord_hip check in.colord` and `colord_hip info in.colord`: the reference's
 // runDecompression (src/colord/decompression.cpp:84-258: the FASTQ / FASTA writers) and runInfo (info.cpp:24-53) on top of the
 // record stream of reader.hpp (the library's decoders behind the reference's decompression driver).  FASTA is written when the
-// archive has no `qual` stream.  No GPU is needed to decompress.
+// archive has no `qual` stream.  No GPU is needed to decompress.  An archive with a `hipdigest` stream (digest_stream.hpp) is checked
+// against it while it is decoded; `check` decodes without writing and prints the digests.
 #include "reader.hpp"
 #include <ctime>
 #include <memory>
@@ -20,6 +21,9 @@ int run_info(int argc, char** argv)
 	time_t t = (time_t)I.time;
 	fprintf(stderr, "version major: %u\nversion minor: %u\nversion patch: %u\ntotal bytes: %llu\ntotal bases: %llu\ntotal reads: %u\ntime: %s\ncommand: %s\n",
 		I.version_major, I.version_minor, I.version_patch, (unsigned long long)I.total_bytes, (unsigned long long)I.total_bases, I.total_reads, asctime(localtime(&t)), I.command_line.c_str());
+	ar.close();
+	DigestSet stored;                                                          // archives written with --digest: the content digests they must decode to
+	if (read_hipdigest(argv[2], stored) > 0) for (int i = 0; i < 3; ++i) if ((stored.flags >> i) & 1) fprintf(stderr, "content digest: %s\n", stored.line(i).c_str());
 	return 0;
 }
 
@@ -39,17 +43,22 @@ static void format_record(std::vector<char>& line, const Record& r, bool is_fast
 		line.insert(line.end(), r.quals, r.quals + r.n_bases); line.push_back('\n');
 	}
 }
+// what decoding an archive gave: its records, and (asked for) the content digests of what the decoders returned
+struct Decoded { uint64_t n_rec = 0; DigestSet computed; size_t domains = 0, at_a_time = 0; };
+
 // Archives with INDEPENDENT model domains (`colord_hip compress-* --domains K`): every domain is decoded by a worker of its own — three
 // stream threads each, as for a whole archive — into a file of its own next to the output; the files are then joined in order.  The ids
-// come from one pass over the `header` stream that all workers share.  Returns the number of records, or -1 if the archive is not of
-// that kind (the caller then decodes it as one stream).
-static long long decompress_domains(const std::string& arc, const std::string& genome, const std::string& out_path, int max_threads)
+// come from one pass over the `header` stream that all workers share.  false: the archive is not of that kind (the caller then decodes
+// it as one stream).  out_path empty: nothing is written (`colord_hip check`).  With want_digest every worker digests its domain's reads
+// at their indices in the whole input and the partial digests are added; the header digest is the shared pass's.
+static bool decode_domains(const std::string& arc, const std::string& genome, const std::string& out_path, int max_threads, bool want_digest, Decoded& D)
 {
 	size_t K = 0; bool is_fastq = true;
-	{ RecordStream probe(arc, genome); if (!probe.independent_domains() || probe.n_domains() < 2) return -1; K = probe.n_domains(); is_fastq = probe.is_fastq(); }
-	HeaderCache hc;
+	{ RecordStream probe(arc, genome); if (!probe.independent_domains() || probe.n_domains() < 2) return false; K = probe.n_domains(); is_fastq = probe.is_fastq(); }
+	const bool writing = !out_path.empty();
+	HeaderCache hc; hc.want_digest = want_digest;
 	std::thread ht([&]() { hc.decode_all(arc); });
-	std::vector<std::string> errs(K), tmp(K); std::vector<uint64_t> n_rec(K, 0);
+	std::vector<std::string> errs(K), tmp(K); std::vector<uint64_t> n_rec(K, 0); std::vector<DigestSet> dig(K);
 	for (size_t d = 0; d < K; ++d) tmp[d] = out_path + ".domain" + std::to_string(d) + ".tmp";
 	// the dna / qual threads of the first `max_threads` domains start at once; the ids are needed from the first record on
 	std::mutex mu; size_t next_dom = 0;
@@ -60,17 +69,19 @@ static long long decompress_domains(const std::string& arc, const std::string& g
 			try
 			{
 				RecordStream r(arc, genome, (int)d, &hc);
+				if (want_digest) r.enable_digest();
 				r.prefetch();
 				{ static std::mutex hm; std::lock_guard<std::mutex> l(hm); if (ht.joinable()) ht.join(); }
 				if (!hc.err.empty()) throw std::runtime_error("header stream: " + hc.err);
-				FILE* out = fopen(tmp[d].c_str(), "wb");
-				if (!out) throw std::runtime_error("cannot open file: " + tmp[d]);
-				std::vector<char> obuf(1 << 22); setvbuf(out, obuf.data(), _IOFBF, obuf.size());
+				FILE* out = writing ? fopen(tmp[d].c_str(), "wb") : nullptr;
+				if (writing && !out) throw std::runtime_error("cannot open file: " + tmp[d]);
+				std::vector<char> obuf(writing ? 1 << 22 : 1); if (out) setvbuf(out, obuf.data(), _IOFBF, obuf.size());
 				std::vector<char> line; Record rec; bool ok = true;
-				while (r.next(rec)) { format_record(line, rec, is_fastq); if (fwrite(line.data(), 1, line.size(), out) != line.size()) { ok = false; break; } ++n_rec[d]; }
-				if (fflush(out) != 0 || ferror(out)) ok = false;
-				if (fclose(out) != 0) ok = false;
+				while (r.next(rec)) { if (out) { format_record(line, rec, is_fastq); if (fwrite(line.data(), 1, line.size(), out) != line.size()) { ok = false; break; } } ++n_rec[d]; }
+				if (out && (fflush(out) != 0 || ferror(out))) ok = false;
+				if (out && fclose(out) != 0) ok = false;
 				if (!ok) throw std::runtime_error("cannot write " + tmp[d] + " (disk full?)");
+				if (want_digest) dig[d] = r.digests();
 			}
 			catch (const std::exception& e) { errs[d] = e.what(); }
 		}
@@ -79,59 +90,113 @@ static long long decompress_domains(const std::string& arc, const std::string& g
 	std::vector<std::thread> th; for (size_t i = 0; i < T; ++i) th.emplace_back(worker);
 	for (auto& t : th) t.join();
 	if (ht.joinable()) ht.join();
-	for (size_t d = 0; d < K; ++d) if (!errs[d].empty()) { for (auto& t : tmp) remove(t.c_str()); die("domain " + std::to_string(d) + ": " + errs[d]); }
+	for (size_t d = 0; d < K; ++d) if (!errs[d].empty()) { if (writing) for (auto& t : tmp) remove(t.c_str()); die("domain " + std::to_string(d) + ": " + errs[d]); }
+	for (size_t d = 0; d < K; ++d) { D.n_rec += n_rec[d]; D.computed.flags |= dig[d].flags; D.computed.add(0, dig[d].d[0]); D.computed.add(1, dig[d].d[1]); }
+	if (want_digest) { D.computed.flags |= 4u; D.computed.add(2, hc.digest); }
+	D.domains = K; D.at_a_time = T;
+	if (!writing) return true;
 	FILE* out = fopen(out_path.c_str(), "wb");
 	if (!out) die("cannot open file: " + out_path);
-	std::vector<char> buf(1 << 24); uint64_t total = 0; bool ok = true;
+	std::vector<char> buf(1 << 24); bool ok = true;
 	for (size_t d = 0; d < K && ok; ++d)
 	{
 		FILE* in = fopen(tmp[d].c_str(), "rb");
 		if (!in) { ok = false; break; }
 		for (size_t got; (got = fread(buf.data(), 1, buf.size(), in)) > 0; ) if (fwrite(buf.data(), 1, got, out) != got) { ok = false; break; }
 		fclose(in); remove(tmp[d].c_str());
-		total += n_rec[d];
 	}
 	if (fflush(out) != 0 || ferror(out)) ok = false;
 	if (fclose(out) != 0) ok = false;
 	if (!ok) die("cannot write " + out_path + " (disk full?)");
-	fprintf(stderr, "colord_hip: %llu records decompressed (%zu independent domains, %zu at a time)\n", (unsigned long long)total, K, T);
-	return (long long)total;
+	return true;
+}
+
+// The records of an archive in file order, written to out_path (empty: decoded only).  remove_on_error: a decoding error takes the
+// output file with it (an archive whose content digest is being checked leaves no half-written or unconfirmed file behind).
+static void decode_archive(const std::string& arc, const std::string& genome, const std::string& out_path, int dom_threads, bool want_digest, bool remove_on_error, Decoded& D)
+{
+	auto fail = [&](const std::string& m) { if (remove_on_error && !out_path.empty()) (void)remove(out_path.c_str()); die(m); };
+	try { if (decode_domains(arc, genome, out_path, dom_threads, want_digest, D)) return; } catch (const std::exception& e) { fail(e.what()); }
+	bool write_ok = true;
+	try
+	{
+		RecordStream rs(arc, genome);
+		if (want_digest) rs.enable_digest();
+		FILE* out = out_path.empty() ? nullptr : fopen(out_path.c_str(), "wb");
+		if (!out_path.empty() && !out) die("cannot open file: " + out_path);
+		std::vector<char> obuf(out ? 1 << 24 : 1); if (out) setvbuf(out, obuf.data(), _IOFBF, obuf.size());
+		const bool is_fastq = rs.is_fastq();
+		// writer (decompression.cpp:84-258): records in file order; the three streams are packed independently
+		std::vector<char> line; Record r;
+		try
+		{
+			while (rs.next(r))
+			{
+				if (out) { format_record(line, r, is_fastq); if (fwrite(line.data(), 1, line.size(), out) != line.size()) { write_ok = false; break; } }
+				++D.n_rec;
+			}
+		}
+		catch (...) { if (out) fclose(out); throw; }
+		if (out && (fflush(out) != 0 || ferror(out))) write_ok = false;
+		if (out && fclose(out) != 0) write_ok = false;
+		if (want_digest && write_ok) D.computed = rs.digests();
+	}
+	catch (const std::exception& e) { fail(e.what()); }
+	if (!write_ok) fail("cannot write " + out_path + " (disk full?)");
 }
 
 int run_decompress(int argc, char** argv)
 {
 	std::vector<std::string> pos; std::string genome; int dom_threads = (int)std::min<unsigned>(16, std::max<unsigned>(1, std::thread::hardware_concurrency() / 3));
+	bool ignore_digest = false;
 	for (int i = 2; i < argc; ++i)
 	{
 		const std::string a = argv[i];
 		if ((a == "-G" || a == "--reference-genome") && i + 1 < argc) genome = argv[++i];      // needed when the archive was written with -G but without -s
 		else if (a == "-v" || a == "--verbose") ;
 		else if ((a == "-t" || a == "--threads") && i + 1 < argc) dom_threads = atoi(argv[++i]);
+		else if (a == "--ignore-digest") ignore_digest = true;                                  // salvage: decode whatever the stored content digest says
 		else pos.push_back(a);
 	}
-	if (pos.size() != 2) { fprintf(stderr, "usage: colord_hip decompress [-G reference_genome.fa] archive.colord output.fastq\n"); return 1; }
-	uint64_t n_rec = 0; bool write_ok = true;
-	try { if (decompress_domains(pos[0], genome, pos[1], dom_threads) >= 0) return 0; } catch (const std::exception& e) { die(e.what()); }
-	try
+	if (pos.size() != 2) { fprintf(stderr, "usage: colord_hip decompress [-G reference_genome.fa] [--ignore-digest] archive.colord output.fastq\n"); return 1; }
+	// an archive written with --digest is checked while it is decoded: the stream threads digest what they decode
+	DigestSet stored; const int have = ignore_digest ? 0 : read_hipdigest(pos[0], stored);
+	if (have < 0) die("the archive's `hipdigest` stream is not one this build reads (--ignore-digest decodes without the check)");
+	Decoded D;
+	decode_archive(pos[0], genome, pos[1], dom_threads, have > 0, have > 0, D);
+	if (have > 0)
 	{
-		RecordStream rs(pos[0], genome);
-		FILE* out = fopen(pos[1].c_str(), "wb");
-		if (!out) die("cannot open file: " + pos[1]);
-		std::vector<char> obuf(1 << 24); setvbuf(out, obuf.data(), _IOFBF, obuf.size());
-		const bool is_fastq = rs.is_fastq();
-		// writer (decompression.cpp:84-258): records in file order; the three streams are packed independently
-		std::vector<char> line; Record r;
-		while (rs.next(r))
-		{
-			format_record(line, r, is_fastq);
-			if (fwrite(line.data(), 1, line.size(), out) != line.size()) { write_ok = false; break; }
-			++n_rec;
-		}
-		if (fflush(out) != 0 || ferror(out)) write_ok = false;
-		if (fclose(out) != 0) write_ok = false;
+		const std::string bad = digest_mismatch(stored, D.computed);
+		if (!bad.empty()) { (void)remove(pos[1].c_str()); die("content digest mismatch, the archive does not hold what was compressed: " + bad + " (no output was written; --ignore-digest decodes regardless)"); }
+		fprintf(stderr, "content digest: ok (%s)\n", stored.names().c_str());
 	}
-	catch (const std::exception& e) { die(e.what()); }
-	if (!write_ok) die("cannot write " + pos[1] + " (disk full?)");
-	fprintf(stderr, "colord_hip: %llu records decompressed\n", (unsigned long long)n_rec);
+	if (D.domains) fprintf(stderr, "colord_hip: %llu records decompressed (%zu independent domains, %zu at a time)\n", (unsigned long long)D.n_rec, D.domains, D.at_a_time);
+	else fprintf(stderr, "colord_hip: %llu records decompressed\n", (unsigned long long)D.n_rec);
+	return 0;
+}
+
+// `colord_hip check archive.colord [-G genome]`: decodes everything, writes nothing; the content digests of what was decoded, the stored
+// ones where the archive has them (also archives of the reference, which have none), exit 1 where they differ or the archive does not decode
+int run_check(int argc, char** argv)
+{
+	std::vector<std::string> pos; std::string genome; int dom_threads = (int)std::min<unsigned>(16, std::max<unsigned>(1, std::thread::hardware_concurrency() / 3));
+	for (int i = 2; i < argc; ++i)
+	{
+		const std::string a = argv[i];
+		if ((a == "-G" || a == "--reference-genome") && i + 1 < argc) genome = argv[++i];
+		else if ((a == "-t" || a == "--threads") && i + 1 < argc) dom_threads = atoi(argv[++i]);
+		else pos.push_back(a);
+	}
+	if (pos.size() != 1) { fprintf(stderr, "usage: colord_hip check [-G reference_genome.fa] archive.colord\n"); return 1; }
+	DigestSet stored; const int have = read_hipdigest(pos[0], stored);
+	Decoded D;
+	decode_archive(pos[0], genome, "", dom_threads, true, false, D);
+	for (int i = 0; i < 3; ++i) printf("%s\n", D.computed.line(i).c_str());
+	if (have == 0) { printf("no content digest is stored in this archive (written without --digest); %llu records decode\n", (unsigned long long)D.n_rec); return 0; }
+	if (have < 0) { printf("the archive's `hipdigest` stream is not one this build reads\n"); return 1; }
+	for (int i = 0; i < 3; ++i) if ((stored.flags >> i) & 1) printf("stored %s\n", stored.line(i).c_str());
+	const std::string bad = digest_mismatch(stored, D.computed);
+	if (!bad.empty()) { printf("content digest mismatch: %s\n", bad.c_str()); return 1; }
+	printf("content digest: ok (%s)\n", stored.names().c_str());
 	return 0;
 }

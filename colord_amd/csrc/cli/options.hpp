@@ -37,6 +37,7 @@ struct Options {
 	int domains = 1;                                // --domains K: K INDEPENDENT model domains on one GPU (own k-mer set, references, index, models each): decoded side by side
 	bool verify_scripts = false;                    // --verify-scripts: cl_ctx_set_verify on every compressor's context
 	bool verify_streams = false;                    // --verify-streams: cl_ctx_set_verify_streams on every compressor's context
+	bool digest = false;                            // --digest: content digests of the input (cl_ctx_set_digest; ids on the host) in a `hipdigest` stream
 	int gpus = 1; std::vector<int> gpu_list; std::string transport = "rccl";   // --gpus N [--gpu-list a,b,..] [--transport rccl|host]: reads sharded over N GPUs (run_compress_multi)
 	Preset P{}; QDef qd;                            // resolved by parse_options: the preset of source and priority with the options laid over it, the quality thresholds / representatives
 	int argc = 0; char** argv = nullptr;            // the command line as given (`info` stream)
@@ -46,7 +47,7 @@ inline void usage()
 {
 	fprintf(stderr,
 		"usage: colord_hip compress-ont|compress-pbhifi|compress-pbraw [options] input.fastq|fasta[.gz] output.colord\n"
-		"       colord_hip decompress archive.colord output.fastq\n       colord_hip info archive.colord\n"
+		"       colord_hip decompress [--ignore-digest] archive.colord output.fastq\n       colord_hip check archive.colord\n       colord_hip info archive.colord\n"
 		"options (as the reference, arg_parse.cpp:455-640):\n"
 		"  -p,--priority ratio|balanced|memory   -k,--kmer-len K with -a,--anchor-len A (both or none)\n"
 		"  -q,--qual org|none|avg|2-fix|4-fix|5-fix|2-avg|4-avg|5-avg   -T,--qual-thresholds a,b,..   -D,--qual-values a,b,..\n"
@@ -64,6 +65,11 @@ inline void usage()
 		"  --verify-streams   each coded part of the dna and qual streams is decoded on the device with the decoder's interval arithmetic: every symbol must fall in the interval\n"
 		"                     its model gave it and the part must end at its size; the models themselves are not replayed (edit scripts -> sort keys -> triples is not covered)\n"
 		"                     (a part that does not decode: message, no archive, non-zero exit)\n"
+		"  --digest           content digests of the input — bases and quality symbols digested on the device before any kernel of the compressor touches them, ids on the host —\n"
+		"                     are stored in the archive (stream `hipdigest`, 80 bytes; the reference's decompressor ignores it).  `colord_hip decompress` recomputes them from what it\n"
+		"                     decodes: a difference is a message naming the stream, no output file and exit 1 (--ignore-digest decodes regardless); `colord_hip check` decodes without\n"
+		"                     writing and prints them.  Same digest with any --part-symbols, --stream-input, --domains, --gpus.  Covered: input -> ... -> decoded symbols; the quality\n"
+		"                     VALUES made from the symbols (-D values, error diffusion of *-avg) are not.  Cost: one pass over 1.4 bytes per base per chunk (not measured on a GPU yet)\n"
 		"  --domains K        K independent model domains (equal shares of the reads, each compressed on its own): `colord_hip decompress`\n"
 		"                     decodes them side by side; costs archive size (own k-mer statistics and reference reads per domain)\n"
 		"  --gpus N [--gpu-list a,b,..] [--transport rccl|host]   reads sharded over N GPUs, one host thread and one model domain per GPU;\n"
@@ -120,6 +126,7 @@ inline Options parse_options(int argc, char** argv)
 		else if (a == "--stream-input") O.stream_input = true;
 		else if (a == "--verify-scripts") O.verify_scripts = true;
 		else if (a == "--verify-streams") O.verify_streams = true;
+		else if (a == "--digest") O.digest = true;
 		else if (a == "--parse-threads") { O.parse_threads = atoi(need(i).c_str()); if (O.parse_threads < 1 || O.parse_threads > 256) die("--parse-threads must be in [1, 256]"); }
 		else if (a == "-h" || a == "--help") { usage(); exit(0); }
 		else if (!a.empty() && a[0] == '-' && a.size() > 1) die("unknown option " + a);

@@ -11,6 +11,7 @@
 #include "colord_hip.h"
 #include "archive.hpp"
 #include "genome_io.hpp"
+#include "digest_stream.hpp"
 #include <condition_variable>
 #include <deque>
 #include <mutex>
@@ -84,6 +85,7 @@ struct Record { const uint8_t* header; size_t header_len; const uint8_t* bases; 
 // the whole file, entr_header.cpp:46-80)
 struct HeaderCache {
 	std::vector<uint8_t> ids; std::vector<uint64_t> off{ 0 }; std::vector<uint8_t> plus; std::string err;
+	bool want_digest = false; cl_digest digest{ 0, 0, 0 };                   // the header digest of all ids (content digest, digest_stream.hpp)
 	void decode_all(const std::string& path)
 	{
 		ArchiveReader ar; if (!ar.open(path)) { err = "cannot open archive: " + path; return; }
@@ -93,7 +95,9 @@ struct HeaderCache {
 		try
 		{
 			if (s_hdr < 0 || s_meta < 0 || !ar.part(s_meta, 0, mb, mm)) throw std::runtime_error("header / meta stream missing");
-			const Meta M = parse_meta(mb, ar.id("qual") >= 0);
+			const bool fastq = ar.id("qual") >= 0;
+			const Meta M = parse_meta(mb, fastq);
+			DigestFeed feed;
 			if (cl_id_decoder_create(M.header_mode, &c) != CL_OK) throw std::runtime_error("cl_id_decoder_create");
 			for (size_t p = 0; p < ar.n_parts(s_hdr); ++p)
 			{
@@ -105,7 +109,9 @@ struct HeaderCache {
 				const uint64_t base = ids.size();
 				ids.insert(ids.end(), buf.begin(), buf.begin() + got); plus.insert(plus.end(), pl.begin(), pl.end());
 				for (uint64_t i = 1; i <= n; ++i) off.push_back(base + o[i]);
+				if (want_digest) for (uint64_t i = 0; i < n; ++i) { for (uint64_t j = o[i]; j < o[i + 1]; ++j) feed.push(buf[j]); feed.push(fastq && pl[i] ? 1 : 0); feed.end_read(DG_HEADER); }
 			}
+			digest = feed.d;
 		}
 		catch (const std::exception& e) { err = e.what(); }
 		if (c) cl_id_decoder_free(c);
@@ -121,6 +127,9 @@ class RecordStream {
 	// so it is decoded by a DNA decoder of its own (with its own sparse range) — and K of them side by side (cli/decompress.cpp)
 	bool independent = false; std::vector<uint64_t> dom_part{ 0 }, dom_read{ 0 }; std::vector<uint32_t> dom_sparse;
 	int only_domain = -1; const HeaderCache* ext_hdr = nullptr; uint64_t read_index = 0;
+	// content digest (digest_stream.hpp): each stream thread digests what it decodes, read by read from the first read it decodes on
+	bool want_digest = false; cl_digest dig_dna{ 0, 0, 0 }, dig_qual{ 0, 0, 0 }, dig_hdr{ 0, 0, 0 };
+	uint64_t first_read_index() const { return only_domain >= 0 ? dom_read[only_domain] : 0; }
 	size_t part_begin() const { return only_domain >= 0 ? (size_t)dom_part[only_domain] : 0; }
 	size_t part_end() const { return only_domain >= 0 && (size_t)only_domain + 1 < dom_part.size() ? (size_t)dom_part[only_domain + 1] : ar.n_parts(s_dna); }
 	genome_io::Sequences pseudo;                                          // reference-genome mode: the pseudo reads that precede the first read
@@ -139,6 +148,10 @@ public:
 	explicit RecordStream(const std::string& path, const std::string& genome_path = "", int only_domain = -1, const HeaderCache* headers = nullptr);
 	bool independent_domains() const { return independent; }
 	size_t n_domains() const { return dom_part.size(); }
+	// before the first record is asked for: the stream threads digest what they decode.  digests(): after next() has returned false —
+	// dna, qual (flag off without a quality stream or in mode none, which decodes nothing) and header (not with external ids: theirs is the cache's)
+	void enable_digest() { if (!started) want_digest = true; }
+	DigestSet digests() const { DigestSet s; s.flags = 1u | (fastq && M.qual_mode != 8 ? 2u : 0u) | (ext_hdr ? 0u : 4u); s.d[0] = dig_dna; s.d[1] = dig_qual; s.d[2] = dig_hdr; return s; }
 	void prefetch() { if (!started) start(); }                           // starts the decoder threads before the first next()
 	~RecordStream() { q_bases_for_qual.abort(); q_reads.abort(); q_quals.abort(); q_hdr.abort(); join(); ar.close(); }
 	RecordStream(const RecordStream&) = delete; RecordStream& operator=(const RecordStream&) = delete;
@@ -221,7 +234,7 @@ inline void RecordStream::start()
 		for (size_t i = 0; d && i + 1 < pseudo.off.size(); ++i)                    // decompression_common.cpp:287-292
 			if (cl_dna_decoder_add_ref(d, pseudo.codes.data() + pseudo.off[i], (uint32_t)(pseudo.off[i + 1] - pseudo.off[i])) != CL_OK) { err_dna = "cl_dna_decoder_add_ref"; break; }
 		if (!err_dna.empty() && d) { cl_dna_decoder_free(d); d = nullptr; }
-		std::vector<uint8_t> in; uint64_t n_reads = 0;
+		std::vector<uint8_t> in; uint64_t n_reads = 0, g = first_read_index();
 		for (size_t p = p_first; d && p < n_parts; ++p)
 		{
 			if (!ar.part(s_dna, p, in, n_reads)) { err_dna = "cannot read a `dna` part"; break; }
@@ -243,6 +256,7 @@ inline void RecordStream::start()
 			if (s == CL_E_CAPACITY) { x.bases.resize(got); s = cl_dna_decode_part(d, in.data(), in.size(), (uint32_t)n_reads, x.bases.data(), got, x.off.data(), &got); }   // the decoded part is kept inside
 			if (s != CL_OK) { err_dna = cl_dna_decoder_error(d); break; }
 			x.bases.resize(got);
+			if (want_digest) { if (!dg_bases_host(x.bases.data(), x.off.data(), n_reads, g, &dig_dna)) { err_dna = "more reads than the content digest can index"; break; } g += n_reads; }
 			if (fastq) { ReadPart cp; cp.bases = x.bases; cp.off = x.off; q_bases_for_qual.push(std::move(cp)); }
 			q_reads.push(std::move(x));
 		}
@@ -257,6 +271,7 @@ inline void RecordStream::start()
 		for (size_t i = 0; i < M.rev.size(); ++i) qpar.rev[i] = M.rev[i];
 		cl_qual_decoder* q = nullptr;
 		if (cl_qual_decoder_create(&qpar, &q) != CL_OK) { err_qual = "cl_qual_decoder_create"; }
+		if (q && want_digest && cl_qual_decoder_set_digest(q, 1, first_read_index()) != CL_OK) { err_qual = "cl_qual_decoder_set_digest"; cl_qual_decoder_free(q); q = nullptr; }
 		ReadPart x; std::vector<uint8_t> in; uint64_t meta = 0; size_t p = part_begin(); const size_t p_first = p;
 		try {
 		while (q && q_bases_for_qual.pop(x))
@@ -271,6 +286,7 @@ inline void RecordStream::start()
 		}
 		} catch (const std::exception& e) { err_qual = std::string("corrupt `qual` part (") + e.what() + ")"; }
 		while (q_bases_for_qual.pop(x)) {}                                    // drain after an error so that the producer can finish
+		if (q && want_digest) (void)cl_qual_decoder_digest(q, &dig_qual);
 		if (q) cl_qual_decoder_free(q);
 		thread_report("qual");
 		q_quals.finish();
@@ -279,7 +295,7 @@ inline void RecordStream::start()
 	t_hdr = std::thread([this]() {
 		cl_id_decoder* c = nullptr;
 		if (cl_id_decoder_create(M.header_mode, &c) != CL_OK) { err_hdr = "cl_id_decoder_create"; }
-		std::vector<uint8_t> in; uint64_t n = 0;
+		std::vector<uint8_t> in; uint64_t n = 0; DigestFeed feed;
 		try {
 		for (size_t p = 0; c && p < ar.n_parts(s_hdr); ++p)
 		{
@@ -292,9 +308,11 @@ inline void RecordStream::start()
 			if (s == CL_E_CAPACITY) { x.ids.resize(got); s = cl_id_decode_part(c, in.data(), in.size(), (uint32_t)n, x.ids.data(), got, x.off.data(), x.plus.data(), &got); }
 			if (s != CL_OK) { err_hdr = "corrupt `header` part"; break; }
 			x.ids.resize(got);
+			if (want_digest) for (uint64_t i = 0; i < n; ++i) { for (uint64_t j = x.off[i]; j < x.off[i + 1]; ++j) feed.push(x.ids[j]); feed.push(fastq && x.plus[i] ? 1 : 0); feed.end_read(DG_HEADER); }
 			q_hdr.push(std::move(x));
 		}
 		} catch (const std::exception& e) { err_hdr = std::string("corrupt `header` part (") + e.what() + ")"; }
+		dig_hdr = feed.d;
 		if (c) cl_id_decoder_free(c);
 		thread_report("header");
 		q_hdr.finish();

@@ -346,6 +346,8 @@ struct cl_ctx {
 	std::atomic<uint64_t> verified_reads{ 0 }, verified_bases{ 0 };   // what this context has checked so (cl_ctx_verified adds the encode lanes')
 	bool verify_streams = false;                 // cl_ctx_set_verify_streams: the DNA and quality coders run every coded part through the decoder's interval arithmetic (rc_check.hpp)
 	std::atomic<uint64_t> verified_stream_parts{ 0 }, verified_stream_symbols{ 0 }, verified_stream_bytes{ 0 };   // what the coders on this context have checked so
+	bool digest = false;                         // cl_ctx_set_digest: cl_compress_shard / cl_compressor_encode on this context digest their input (digest.hip)
+	cl_digest digest_dna{ 0, 0, 0 }, digest_qual{ 0, 0, 0 };   // the totals so far (owner thread only)
 	std::map<std::string, KernelTime> times;     // per-kernel accumulated HIP-event time of the last API call
 	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
 	std::vector<double> pending_bytes, pending_cells;

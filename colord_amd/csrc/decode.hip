@@ -9,6 +9,7 @@
 // models matters, and it is the reference's (the same partition the device encoders use; byte-identical streams prove it).
 #include "common.hpp"
 #include "host_coder.hpp"
+#include "digest.hpp"
 #include <cmath>
 #include <random>
 #include <string>
@@ -337,6 +338,7 @@ struct cl_qual_decoder {
 	uint32_t map_fwd[96] = {}, map_rev[96] = {}, quant[96] = {};
 	uint32_t n_ctx_sym = 0, bits_per_sym = 0, ctx_bits = 0, n_bins = 0; uint64_t ctx_mask = 0; uint32_t n_sym = 0;
 	Family sym, bytes; RangeDec rc; std::string err;
+	bool digest_on = false; DigestFeed dg;                                                    // cl_qual_decoder_set_digest: the symbols of every read as they leave the models
 	void init_models()
 	{
 		if (mode == 0) sym.init(96, 1u << 20, 32, ctx_bits + 11); else sym.init(n_sym, 1u << 18, 8, ctx_bits + 10);      // quality_coder.h:36-39 (contexts: history + bases + flags)
@@ -347,6 +349,7 @@ struct cl_qual_decoder {
 	double dec_avg(uint64_t ctx_base)                                                         // quality_coder_impl.cpp:837-849
 	{
 		const uint32_t a1 = bytes.decode(rc, ctx_base), a2 = bytes.decode(rc, a1 + 0x100ULL);
+		if (digest_on) { dg.push((uint8_t)a1); dg.push((uint8_t)a2); }
 		return (double)((a1 << 8) + a2) / 256.0;
 	}
 	void decode_read(const uint8_t* b, uint32_t len, uint8_t* out);
@@ -371,7 +374,8 @@ void cl_qual_decoder::decode_read(const uint8_t* b, uint32_t len, uint8_t* out)
 			if (i + 1 < len) c += B(i + 1) << sh;
 			sh += 2;
 			c += flag_bits(b[i]) << sh;
-			const uint32_t v = map_rev[sym.decode(rc, c)];
+			const uint32_t s = sym.decode(rc, c), v = map_rev[s];
+			if (digest_on) dg.push((uint8_t)s);
 			out[i] = (uint8_t)(v + 33);
 			hist = ((hist << bits_per_sym) + quant[v]) & ctx_mask;
 		}
@@ -394,6 +398,7 @@ void cl_qual_decoder::decode_read(const uint8_t* b, uint32_t len, uint8_t* out)
 			dna <<= 2; if (i + 1 < len) dna += B(i + 1);
 			dna &= 0xff;
 			const uint32_t d = sym.decode(rc, hist + (dna << ctx_bits) + (flag_bits(b[i]) << (ctx_bits + 8)));
+			if (digest_on) dg.push((uint8_t)d);
 			as[d] += avg[d];
 			const uint32_t v = (uint32_t)(as[d] - qs[d]);
 			qs[d] += v;
@@ -414,6 +419,7 @@ void cl_qual_decoder::decode_read(const uint8_t* b, uint32_t len, uint8_t* out)
 		sh += 2;
 		c += flag_bits(b[i]) << sh;
 		const uint32_t d = sym.decode(rc, c);
+		if (digest_on) dg.push((uint8_t)d);
 		out[i] = (uint8_t)(map_rev[d] + 33);
 		hist = ((hist << bits_per_sym) + d) & ctx_mask;
 	}
@@ -466,7 +472,23 @@ extern "C" cl_status cl_qual_decode_part(cl_qual_decoder* q, const uint8_t* h_in
 {
 	if (!q || !h_off || (n_reads && h_off[n_reads] && (!h_bases || !h_quals))) return CL_E_INVALID;
 	if (q->mode != 8) { if (n_in < 8 || !h_in) return CL_E_INVALID; q->rc.start(h_in, n_in); }
-	for (uint32_t i = 0; i < n_reads; ++i) q->decode_read(h_bases + h_off[i], (uint32_t)(h_off[i + 1] - h_off[i]), h_quals + h_off[i]);
+	for (uint32_t i = 0; i < n_reads; ++i)
+	{
+		q->decode_read(h_bases + h_off[i], (uint32_t)(h_off[i + 1] - h_off[i]), h_quals + h_off[i]);
+		if (q->digest_on && q->mode != 8) q->dg.end_read(DG_QUAL);                  // (mode none: nothing was decoded)
+	}
+	return CL_OK;
+}
+extern "C" cl_status cl_qual_decoder_set_digest(cl_qual_decoder* q, int on, uint64_t first_read)
+{
+	if (!q || first_read >= (1ULL << 63)) return CL_E_INVALID;
+	q->digest_on = on != 0; q->dg = DigestFeed(); q->dg.g = first_read;
+	return CL_OK;
+}
+extern "C" cl_status cl_qual_decoder_digest(const cl_qual_decoder* q, cl_digest* out)
+{
+	if (!q || !out) return CL_E_INVALID;
+	*out = q->dg.d;
 	return CL_OK;
 }
 

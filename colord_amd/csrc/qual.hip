@@ -20,6 +20,7 @@
 #include "objects.hpp"
 #include "rc_dev.hpp"
 #include "rc_check.hpp"    // the opt-in check of the coded parts (cl_ctx_set_verify_streams)
+#include "digest.hpp"      // qual_bin_map
 #include <algorithm>
 
 namespace {
@@ -73,6 +74,7 @@ struct QualPrepared {
 struct cl_qual_coder {
 	cl_ctx* ctx = nullptr;
 	QualCfg cfg;
+	cl_qual_params prm{};         // as given to cl_qual_coder_create (the content digest derives the symbols from them on its own)
 	DevBuf<QualCfg> d_cfg;
 	DevBuf<uint32_t> state;       // per-base family: n_ctx * (n_sym + 1)  (counters..., total)
 	DevBuf<uint32_t> bstate;      // byte family: 896 * 257
@@ -415,7 +417,7 @@ extern "C" cl_status cl_qual_coder_create(cl_ctx* ctx, const cl_qual_params* prm
 	if (prm->mode < 0 || prm->mode > QM_NONE || prm->source < 0 || prm->source > 2 || prm->level < 1 || prm->level > 3)
 		return cl_fail(ctx, CL_E_INVALID, "cl_qual_coder_create: mode 0..8, source 0..2, level 1..3");
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	cl_qual_coder* Q = new cl_qual_coder(); Q->ctx = ctx;
+	cl_qual_coder* Q = new cl_qual_coder(); Q->ctx = ctx; Q->prm = *prm;
 	std::unique_ptr<cl_qual_coder> guard(Q);
 	QualCfg& c = Q->cfg; memset(&c, 0, sizeof(c));
 	c.mode = prm->mode; c.level = prm->level;
@@ -424,9 +426,7 @@ extern "C" cl_status cl_qual_coder_create(cl_ctx* ctx, const cl_qual_params* prm
 		if (prm->n_fwd != n - 1) return cl_fail(ctx, CL_E_INVALID, "cl_qual_coder_create: need " + std::to_string(n - 1) + " thresholds");
 		for (uint32_t i = 0; i + 1 < n - 1; ++i) if (prm->fwd[i] > prm->fwd[i + 1]) return cl_fail(ctx, CL_E_INVALID, "thresholds must ascend");
 		if (prm->fwd[n - 2] > 96) return cl_fail(ctx, CL_E_INVALID, "threshold > 96");
-		fill_range(c.map_fwd, 0, (int)prm->fwd[0], 0);
-		for (uint32_t b = 1; b + 1 < n; ++b) fill_range(c.map_fwd, (int)prm->fwd[b - 1], (int)prm->fwd[b], (uint8_t)b);
-		fill_range(c.map_fwd, (int)prm->fwd[n - 2], 96, (uint8_t)(n - 1));
+		qual_bin_map(c.map_fwd, prm->fwd, n);                                 // (shared with the content digest, which derives the symbols on its own)
 		c.n_bins = n; c.n_sym = n;
 		return CL_OK;
 	};
@@ -480,6 +480,7 @@ extern "C" cl_status cl_qual_coder_create(cl_ctx* ctx, const cl_qual_params* prm
 	return CL_OK;
 }
 extern "C" cl_ctx* cl_qual_coder_ctx(const cl_qual_coder* q) { return q ? q->ctx : nullptr; }
+const cl_qual_params* cl_qual_coder_params(const cl_qual_coder* q) { return q ? &q->prm : nullptr; }
 extern "C" void cl_qual_coder_free(cl_qual_coder* q) { delete q; }
 
 // CEntrComprQuals::Compress for a batch of whole parts (entr_qual.h:100-135).  Models persist across calls.

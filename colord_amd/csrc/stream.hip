@@ -376,6 +376,11 @@ extern "C" cl_status cl_compressor_encode(cl_compressor* c, const cl_reads* read
 	// the chunk leaves the look-ahead window whatever happens below (lanes may go on to the next announced chunk)
 	struct Advance { cl_compressor* c; size_t idx; ~Advance() { { std::lock_guard<std::mutex> l(c->la.lane_mu); c->la.prepared.erase(idx); c->bounds[idx].release(); c->enc_chunk = idx + 1; } c->la.lane_cv.notify_all(); } } adv{ c, idx };
 	if (!n) return CL_OK;
+	if (ctx->digest)
+	{	// the content digest of the chunk, from the input, at its reads' indices in the whole input, before the coders start
+		uint64_t g = c->first_read; for (size_t i = 0; i < idx; ++i) g += c->chunk_reads[i];
+		CL_TRY(digest_chunk(ctx, reads, c->has_qual ? &c->Q : nullptr, d_quals, d_base_off, g));
+	}
 	struct HooksOff { cl_compressor* c; ~HooksOff() { cl_dna_set_before_tail(c->dna, nullptr); cl_qual_set_before_tail(c->qual, nullptr); } } hooks_off{ c };
 	ChunkCoder coder(ctx, c->P.level, c->dna, c->qual, ChunkIO{ reads, d_quals, d_base_off, h_part_bounds, n_parts, d_dna_out, dna_cap, h_dna_part_sizes, d_qual_out, qual_cap, h_qual_part_sizes, info });
 	lookahead_quality(c, job.get(), coder);
@@ -393,6 +398,11 @@ extern "C" cl_status cl_compressor_encode(cl_compressor* c, const cl_reads* read
 extern "C" cl_status cl_compressor_verified(const cl_compressor* c, uint64_t* reads, uint64_t* bases)
 {
 	return c ? cl_ctx_verified(c->ctx, reads, bases) : CL_E_INVALID;
+}
+
+extern "C" cl_status cl_compressor_digest(const cl_compressor* c, cl_digest* dna, cl_digest* qual)
+{
+	return c ? cl_ctx_digest(c->ctx, dna, qual) : CL_E_INVALID;
 }
 
 // every context that codes for the compressor: its own (the DNA stream; the quality stream of levels 2 and 3) and the quality coder's

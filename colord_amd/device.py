@@ -51,7 +51,8 @@ class _OrderedLib:
     COLORD_HIP_SYNC_DEBUG, which shifts the timing): a race of the HARNESS, not of the library's pool.  Waiting on an idle stream costs
     microseconds; a host that embeds the library orders its own streams."""
     _HOST_ONLY = ("cl_last_error", "cl_ctx_kernel_times", "cl_ctx_last_kernel_ms", "cl_ctx_set_timing", "cl_ref_accept", "cl_ctx_set_verify", "cl_ctx_verified",
-                  "cl_compressor_verified", "cl_ctx_set_verify_streams", "cl_ctx_verified_streams", "cl_compressor_verified_streams")
+                  "cl_compressor_verified", "cl_ctx_set_verify_streams", "cl_ctx_verified_streams", "cl_compressor_verified_streams",
+                  "cl_ctx_set_digest", "cl_ctx_digest", "cl_compressor_digest", "cl_digest_bases_host", "cl_digest_bytes_host", "cl_qual_decoder_set_digest", "cl_qual_decoder_digest")
 
     def __init__(self, lib, device):
         self._lib, self._device, self._cache = lib, device, {}
@@ -132,6 +133,33 @@ class Context:
         p, s, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         _check(None, self.lib.cl_ctx_verified_streams(self.h, C.byref(p), C.byref(s), C.byref(b)))
         return p.value, s.value, b.value
+
+    def set_digest(self, on: bool = True):
+        """cl_ctx_set_digest: compress_shard() and compressors of this context digest the bases and quality symbols of their input."""
+        self.lib.cl_ctx_set_digest(self.h, int(bool(on)))
+
+    def digest(self):
+        """cl_ctx_digest: ((reads, symbols, sum) of the dna digest, the same of the qual digest) so far on this context."""
+        d, q = N.Digest(), N.Digest()
+        _check(None, self.lib.cl_ctx_digest(self.h, C.byref(d), C.byref(q)))
+        return d.triple(), q.triple()
+
+    def digest_bases(self, reads: "Reads", first_read: int = 0, acc: "N.Digest | None" = None):
+        """cl_digest_bases: the dna digest of an arena whose first read is read first_read of the input, added to acc; (reads, symbols, sum)."""
+        acc = N.Digest() if acc is None else acc
+        _check(self, self.lib.cl_digest_bases(self.h, reads.h, first_read, C.byref(acc)))
+        return acc.triple()
+
+    def digest_quals(self, reads: "Reads", quals: torch.Tensor, qual_off: torch.Tensor, mode: int, fwd=(), first_read: int = 0, acc: "N.Digest | None" = None):
+        """cl_digest_quals: the qual digest of the symbols a quality coder of `mode` (thresholds fwd) codes for the reads, added to acc."""
+        prm = N.QualParams()
+        prm.mode, prm.source, prm.level, prm.n_fwd = mode, 0, 1, len(fwd)
+        for i, v in enumerate(fwd):
+            prm.fwd[i] = v
+        acc = N.Digest() if acc is None else acc
+        quals, qual_off = quals.contiguous(), qual_off.contiguous()
+        _check(self, self.lib.cl_digest_quals(self.h, C.byref(prm), reads.h, quals.data_ptr() if quals.numel() else None, qual_off.data_ptr(), first_read, C.byref(acc)))
+        return acc.triple()
 
     # ---- arena ----
     def pack_reads(self, codes: torch.Tensor, offsets: torch.Tensor, ascii: bool = False) -> "Reads":
@@ -557,6 +585,12 @@ class Compressor(_Obj):
         p, s, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         _check(None, self.ctx.lib.cl_compressor_verified_streams(self.h, C.byref(p), C.byref(s), C.byref(b)))
         return p.value, s.value, b.value
+
+    def digest(self):
+        """cl_compressor_digest: ((reads, symbols, sum) dna, the same qual) of the chunks encoded so far (Context.set_digest)."""
+        d, q = N.Digest(), N.Digest()
+        _check(None, self.ctx.lib.cl_compressor_digest(self.h, C.byref(d), C.byref(q)))
+        return d.triple(), q.triple()
 
     def genome_add(self, sequences: "Reads"):
         _check(self.ctx, self.ctx.lib.cl_compressor_genome_add(self.h, sequences.h))

@@ -82,6 +82,18 @@ cl_status cl_ctx_verified(const cl_ctx* ctx, uint64_t* reads, uint64_t* bases);
  * its own counts there; cl_compressor_verified_streams adds them up). */
 void cl_ctx_set_verify_streams(cl_ctx* ctx, int on);
 cl_status cl_ctx_verified_streams(const cl_ctx* ctx, uint64_t* parts, uint64_t* symbols, uint64_t* bytes);
+/* Content digest: reads and symbols counted, and a 64-bit sum over the reads that depends on every symbol, on its place
+ * in its read and on the read's index g in the whole input — and on nothing else (not on parts, chunks, lanes, domains or ranks).
+ * Digests of disjoint sets of reads add field by field (wrapping), in any order. */
+typedef struct cl_digest { uint64_t reads, symbols, sum; } cl_digest;
+/* Opt-in digests of the input (off by default; with it off nothing below is launched or allocated and every output byte is the
+ * same).  While it is on, cl_compress_shard on this context (its reads are reads 0 .. n-1) and cl_compressor_encode of a
+ * cl_compressor created on it (every chunk, at its global read index, on this context, before the coders start) add the digests of
+ * the chunk's bases (cl_digest_bases) and, with a quality stream, of its quality symbols (cl_digest_quals) to the context's totals.
+ * They are taken from the input arena and the input quality bytes only, never from anything the encoder made.
+ * cl_ctx_digest: the totals so far (either pointer may be null). */
+void cl_ctx_set_digest(cl_ctx* ctx, int on);
+cl_status cl_ctx_digest(const cl_ctx* ctx, cl_digest* dna, cl_digest* qual);
 
 /* ---- read arena: replaces read_t / read_pack_t (src/colord/utils.h:366-376, in_reads.cpp:24-42) -- */
 /* d_codes: concatenated bases, 1 byte per base; either codes 0..4 (ascii=0) or ASCII ACGTN, upper
@@ -286,6 +298,23 @@ cl_status cl_es_expand(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, c
 cl_status cl_es_verify(cl_ctx* ctx, const cl_reads* reads, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, const uint32_t* d_es_ntuples,
                        uint64_t* n_bad, uint32_t* first_bad);
 
+/* ---- content digests (no counterpart in the reference: its format has no checksum) — on the device, a wave per read ------------- */
+/* The dna digest of every read of the arena, read i being read first_read + i of the input (first_read + n_reads <= 2^63), added to
+ * *acc (host).  A read's words: per 32-base block the arena's packed word and its invalid mask, everything at or behind the read's
+ * end cleared and the packed bits under an N forced to 0; n = bases. */
+cl_status cl_digest_bases(cl_ctx* ctx, const cl_reads* reads, uint64_t first_read, cl_digest* acc);
+/* The qual digest: per read the symbols the quality coder of `qparams` codes for it, in coding order, as bytes, eight to a word
+ * little-endian — org and *-fix: map_fwd[q - 33] per base; *-avg: the 2 x bins average bytes, then the per-base bin symbols; avg: its
+ * two average bytes; none: nothing at all (*acc is left as it is).  d_quals / d_qual_off as for cl_qual_encode; nothing outside
+ * [d_qual_off[r], d_qual_off[r + 1]) is read for read r. */
+cl_status cl_digest_quals(cl_ctx* ctx, const cl_qual_params* qparams, const cl_reads* reads, const uint8_t* d_quals, const uint64_t* d_qual_off,
+                          uint64_t first_read, cl_digest* acc);
+/* The same digests on the HOST, for what a decoder returns.  cl_digest_bases_host: h_codes as cl_dna_decode_part writes them (low
+ * three bits the code, 4 = N; flag bits ignored), h_off n + 1 offsets.  cl_digest_bytes_host: kind 1 dna / 2 qual / 3 header; read i
+ * = the bytes [h_off[i], h_off[i + 1]) of h_bytes (ids followed by their '+' byte; explicit symbol sequences). */
+cl_status cl_digest_bases_host(const uint8_t* h_codes, const uint64_t* h_off, uint64_t n, uint64_t first_read, cl_digest* acc);
+cl_status cl_digest_bytes_host(uint32_t kind, const uint8_t* h_bytes, const uint64_t* h_off, uint64_t n, uint64_t first_read, cl_digest* acc);
+
 /* ---- a14 + a16: CDNACoder / CEntrComprReads (dna_coder.{h,cpp}, entr_read.h:56-80) --------------------- */
 typedef struct cl_dna_coder cl_dna_coder;
 /* CDNACoder::Init(true, maxCandidates, level, ., n_ref_genome_pseudo_reads): one adaptive model set that
@@ -431,6 +460,9 @@ cl_status cl_compressor_verified(const cl_compressor* c, uint64_t* reads, uint64
 /* cl_ctx_verified_streams summed over the contexts that code for the compressor (its own and its quality coder's): the parts, symbols
  * and bytes of the dna and qual streams that were decoded against their models' intervals (cl_ctx_set_verify_streams) */
 cl_status cl_compressor_verified_streams(const cl_compressor* c, uint64_t* parts, uint64_t* symbols, uint64_t* bytes);
+/* cl_ctx_digest of the compressor's context: the digests of the chunks encoded so far (cl_ctx_set_digest); read indices are global:
+ * this rank's first read (cl_compressor_info) + the reads of its chunks before */
+cl_status cl_compressor_digest(const cl_compressor* c, cl_digest* dna, cl_digest* qual);
 
 /* ---- a17, the inverse path: CRangeDecoder (sub_rc.h:216-392), CDNACoder::Decode (dna_coder.cpp:234-437), CQualityCoder::Decode
  *      (quality_coder.cpp:605-657, quality_coder_impl.cpp:506-559,800-849), CIDCoder::Decode (id_coder.cpp:396-600); drivers
@@ -474,6 +506,12 @@ cl_status cl_qual_decoder_new_domain(cl_qual_decoder* q);
  * the same offsets. */
 cl_status cl_qual_decode_part(cl_qual_decoder* q, const uint8_t* h_in, uint64_t n_in, const uint8_t* h_bases, const uint64_t* h_off,
                               uint32_t n_reads, uint8_t* h_quals);
+/* The qual digest of what the decoder decodes (off by default: one flag test per read).  on: from the next read on, read by read,
+ * the symbols as they leave the models — before the -D representatives and the error diffusion turn them into quality values, which
+ * the digest does not cover — and the average bytes are digested, the next read being read first_read of the input; the totals start
+ * from zero.  Mode none decodes nothing and digests nothing.  cl_qual_decoder_digest: the totals so far. */
+cl_status cl_qual_decoder_set_digest(cl_qual_decoder* q, int on, uint64_t first_read);
+cl_status cl_qual_decoder_digest(const cl_qual_decoder* q, cl_digest* out);
 cl_status cl_id_decoder_create(int32_t header_mode, cl_id_decoder** out);
 void cl_id_decoder_free(cl_id_decoder* c);
 /* One `header` part of n ids -> the ids back to back (without '@' / '>'), h_off[n+1], h_plus[n] (1 = the '+' line repeats the id). */
