@@ -185,6 +185,14 @@ _SIG = {
     "cl_dna_encode": (C.c_int32, [_P, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
     "cl_sort_u64": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32]),
     "cl_sort_u64_u32": (C.c_int32, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "cl_sort_u32": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "cl_sort_u32_u32": (C.c_int32, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "cl_sort_swap_u32_u32": (C.c_int32, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
+    "cl_sort_swap_u64_u32": (C.c_int32, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
+    "cl_scan_u32": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cl_scan_u32_u64": (C.c_int32, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cl_run_starts_u32": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cl_run_starts_u64": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

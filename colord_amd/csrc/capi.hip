@@ -204,3 +204,95 @@ extern "C" cl_status cl_sort_u64_u32(cl_ctx* ctx, uint64_t* d_keys, uint32_t* d_
 	cl_timing_collect(ctx);
 	return s;
 }
+
+// The scans and the uint32-key sort as their callers inside the library reach them (scan.hip, sort.hip), for the parity tests.  Every
+// one returns with the context's stream drained: dev_exclusive_scan_u32 / _u64 wait only when they are asked for the total.
+extern "C" cl_status cl_scan_u32(cl_ctx* ctx, uint32_t* d_data, uint64_t n, uint64_t* h_total)
+{
+	if (!ctx || (!d_data && n)) return cl_fail(ctx, CL_E_INVALID, "cl_scan_u32: null argument");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	cl_timing_begin(ctx);
+	cl_status s = dev_exclusive_scan_u32(ctx, d_data, n, h_total);
+	hipError_t e = hipStreamSynchronize(ctx->stream);
+	cl_timing_collect(ctx);
+	if (s == CL_OK) HIP_TRY(ctx, e);
+	return s;
+}
+extern "C" cl_status cl_scan_u32_u64(cl_ctx* ctx, const uint32_t* d_in, uint64_t* d_out, uint64_t n, uint64_t* h_total)
+{
+	if (!ctx || !d_out || (!d_in && n)) return cl_fail(ctx, CL_E_INVALID, "cl_scan_u32_u64: null argument");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	cl_timing_begin(ctx);
+	cl_status s = dev_exclusive_scan_u64(ctx, d_in, d_out, n, h_total);
+	hipError_t e = hipStreamSynchronize(ctx->stream);
+	cl_timing_collect(ctx);
+	if (s == CL_OK) HIP_TRY(ctx, e);
+	return s;
+}
+extern "C" cl_status cl_run_starts_u32(cl_ctx* ctx, const uint32_t* d_keys, uint64_t n, uint32_t shift, uint32_t* d_seg, uint64_t seg_cap, uint64_t* h_n_runs)
+{
+	if (!ctx || !h_n_runs || ((!d_keys || !d_seg) && n)) return cl_fail(ctx, CL_E_INVALID, "cl_run_starts_u32: null argument");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	cl_timing_begin(ctx);
+	cl_status s = dev_run_starts_u32(ctx, d_keys, n, shift, d_seg, seg_cap, h_n_runs);
+	cl_timing_collect(ctx);
+	return s;
+}
+extern "C" cl_status cl_run_starts_u64(cl_ctx* ctx, const uint64_t* d_keys, uint64_t n, uint32_t shift, uint32_t* d_seg, uint64_t seg_cap, uint64_t* h_n_runs)
+{
+	if (!ctx || !h_n_runs || ((!d_keys || !d_seg) && n)) return cl_fail(ctx, CL_E_INVALID, "cl_run_starts_u64: null argument");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	cl_timing_begin(ctx);
+	cl_status s = dev_run_starts_u64(ctx, d_keys, n, shift, d_seg, seg_cap, h_n_runs);
+	cl_timing_collect(ctx);
+	return s;
+}
+extern "C" cl_status cl_sort_u32(cl_ctx* ctx, uint32_t* d_keys, uint64_t n, uint32_t begin_bit, uint32_t end_bit)
+{
+	return cl_sort_u32_u32(ctx, d_keys, nullptr, n, begin_bit, end_bit);
+}
+extern "C" cl_status cl_sort_u32_u32(cl_ctx* ctx, uint32_t* d_keys, uint32_t* d_vals, uint64_t n, uint32_t begin_bit, uint32_t end_bit)
+{
+	if (!ctx || (!d_keys && n)) return cl_fail(ctx, CL_E_INVALID, "cl_sort_u32_u32: null argument");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	cl_timing_begin(ctx);
+	cl_status s = dev_sort_keys32_pairs(ctx, d_keys, d_vals, n, begin_bit, end_bit);
+	cl_timing_collect(ctx);
+	return s;
+}
+// The _swap forms take DevBufs of exactly n elements and may hand them back exchanged with the sort's temporaries: the input goes into two
+// such buffers from the context's pool, and the result is read from whatever they hold afterwards.
+namespace {
+template<typename K, typename Sort>
+cl_status sort_swap_copy(cl_ctx* ctx, const char* who, const K* d_keys_in, const uint32_t* d_vals_in, uint64_t n, uint32_t begin_bit, uint32_t end_bit, K* d_keys_out, uint32_t* d_vals_out, Sort sort)
+{
+	if (!ctx || ((!d_keys_in || !d_vals_in || !d_keys_out || !d_vals_out) && n)) return cl_fail(ctx, CL_E_INVALID, std::string(who) + ": null argument");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	cl_timing_begin(ctx);
+	DevBuf<K> keys; DEV_ALLOC(ctx, keys, n);
+	DevBuf<uint32_t> vals; DEV_ALLOC(ctx, vals, n);
+	if (n)
+	{
+		HIP_TRY(ctx, hipMemcpyAsync(keys.p, d_keys_in, n * sizeof(K), hipMemcpyDeviceToDevice, ctx->stream));
+		HIP_TRY(ctx, hipMemcpyAsync(vals.p, d_vals_in, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+	}
+	cl_status s = sort(ctx, keys, vals, n, begin_bit, end_bit);
+	if (s == CL_OK && n)
+	{
+		HIP_TRY(ctx, hipMemcpyAsync(d_keys_out, keys.p, n * sizeof(K), hipMemcpyDeviceToDevice, ctx->stream));
+		HIP_TRY(ctx, hipMemcpyAsync(d_vals_out, vals.p, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+	}
+	hipError_t e = hipStreamSynchronize(ctx->stream);                           // (the buffers go back to the pool on return)
+	cl_timing_collect(ctx);
+	if (s == CL_OK) HIP_TRY(ctx, e);
+	return s;
+}
+}
+extern "C" cl_status cl_sort_swap_u32_u32(cl_ctx* ctx, const uint32_t* d_keys_in, const uint32_t* d_vals_in, uint64_t n, uint32_t begin_bit, uint32_t end_bit, uint32_t* d_keys_out, uint32_t* d_vals_out)
+{
+	return sort_swap_copy<uint32_t>(ctx, "cl_sort_swap_u32_u32", d_keys_in, d_vals_in, n, begin_bit, end_bit, d_keys_out, d_vals_out, dev_sort_keys32_pairs_swap);
+}
+extern "C" cl_status cl_sort_swap_u64_u32(cl_ctx* ctx, const uint64_t* d_keys_in, const uint32_t* d_vals_in, uint64_t n, uint32_t begin_bit, uint32_t end_bit, uint64_t* d_keys_out, uint32_t* d_vals_out)
+{
+	return sort_swap_copy<uint64_t>(ctx, "cl_sort_swap_u64_u32", d_keys_in, d_vals_in, n, begin_bit, end_bit, d_keys_out, d_vals_out, dev_sort_pairs_swap);
+}

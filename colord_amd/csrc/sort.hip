@@ -176,6 +176,7 @@ cl_status sort_pass(cl_ctx* ctx, const K* kin, const uint32_t* vin, K* kout, uin
 template<typename K>
 cl_status sort_impl(cl_ctx* ctx, K* d_keys, uint32_t* d_vals, uint64_t n, uint32_t begin_bit, uint32_t end_bit, DevBuf<K>* swap_k = nullptr, DevBuf<uint32_t>* swap_v = nullptr)
 {
+	if (end_bit > 8 * sizeof(K)) return cl_fail(ctx, CL_E_INVALID, "radix sort: end_bit " + std::to_string(end_bit) + " is beyond the key's " + std::to_string(8 * sizeof(K)) + " bits");   // (a pass would shift a key by its width)
 	if (n <= 1 || end_bit <= begin_bit) return CL_OK;
 	if (n >= (1ULL << 32)) return cl_fail(ctx, CL_E_UNSUPPORTED, "radix sort: n must be < 2^32 per call");
 	const uint32_t nb = grid_for(n, STILE);

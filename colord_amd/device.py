@@ -444,6 +444,44 @@ class Context:
         else:
             _check(self, self.lib.cl_sort_u64_u32(self.h, keys.data_ptr(), vals.data_ptr(), keys.numel(), begin_bit, end_bit))
 
+    # ---- the device primitives alone (csrc/scan.hip, csrc/sort.hip): int32 / int64 tensors carry uint32 / uint64 bit patterns ----
+    def sort_u32(self, keys: torch.Tensor, vals: torch.Tensor | None = None, begin_bit=0, end_bit=32):
+        assert keys.dtype == torch.int32 and (vals is None or vals.dtype == torch.int32)
+        if vals is None:
+            _check(self, self.lib.cl_sort_u32(self.h, keys.data_ptr(), keys.numel(), begin_bit, end_bit))
+        else:
+            _check(self, self.lib.cl_sort_u32_u32(self.h, keys.data_ptr(), vals.data_ptr(), keys.numel(), begin_bit, end_bit))
+
+    def sort_swap(self, keys: torch.Tensor, vals: torch.Tensor, begin_bit, end_bit):
+        """The coders' form of the sort (buffers that may be swapped with the temporaries): -> (sorted keys, their values); the inputs stay."""
+        assert keys.dtype in (torch.int32, torch.int64) and vals.dtype == torch.int32 and vals.numel() == keys.numel()
+        ko, vo = torch.empty_like(keys), torch.empty_like(vals)
+        f = self.lib.cl_sort_swap_u32_u32 if keys.dtype == torch.int32 else self.lib.cl_sort_swap_u64_u32
+        _check(self, f(self.h, keys.data_ptr(), vals.data_ptr(), keys.numel(), begin_bit, end_bit, ko.data_ptr(), vo.data_ptr()))
+        return ko, vo
+
+    def scan_u32(self, data: torch.Tensor, want_total: bool = True):
+        """In-place exclusive prefix sums of uint32 -> the total (None if not asked for: then a sum beyond 32 bits is not refused)."""
+        assert data.dtype == torch.int32
+        total = C.c_uint64(0)
+        _check(self, self.lib.cl_scan_u32(self.h, data.data_ptr(), data.numel(), C.byref(total) if want_total else None))
+        return total.value if want_total else None
+
+    def scan_u32_u64(self, data: torch.Tensor, out: torch.Tensor, want_total: bool = True):
+        """out[0 .. n] = exclusive prefix sums of the uint32 in data, in 64 bits; out[n] = the total, returned too if asked for."""
+        assert data.dtype == torch.int32 and out.dtype == torch.int64 and out.numel() == data.numel() + 1
+        total = C.c_uint64(0)
+        _check(self, self.lib.cl_scan_u32_u64(self.h, data.data_ptr(), out.data_ptr(), data.numel(), C.byref(total) if want_total else None))
+        return total.value if want_total else None
+
+    def run_starts(self, keys: torch.Tensor, shift: int, seg: torch.Tensor) -> int:
+        """seg[0 .. r] = starts of the runs of equal key >> shift in sorted keys, then n; -> r.  seg must have room for r + 1."""
+        assert keys.dtype in (torch.int32, torch.int64) and seg.dtype == torch.int32
+        f = self.lib.cl_run_starts_u32 if keys.dtype == torch.int32 else self.lib.cl_run_starts_u64
+        r = C.c_uint64(0)
+        _check(self, f(self.h, keys.data_ptr(), keys.numel(), shift, seg.data_ptr(), seg.numel(), C.byref(r)))
+        return r.value
+
 
 class _Obj:
     _free = None

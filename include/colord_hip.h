@@ -526,6 +526,27 @@ cl_status cl_reads_compact(cl_ctx* ctx, const cl_reads* reads, uint32_t read, ui
 /* ---- utilities (device primitives exposed for tests/bench) -------------------------------------- */
 cl_status cl_sort_u64(cl_ctx* ctx, uint64_t* d_keys, uint64_t n, uint32_t begin_bit, uint32_t end_bit);
 cl_status cl_sort_u64_u32(cl_ctx* ctx, uint64_t* d_keys, uint32_t* d_vals, uint64_t n, uint32_t begin_bit, uint32_t end_bit);
+/* Stable LSD radix sort on the key bits [begin_bit, end_bit) — whole keys travel, bits outside the range never order anything;
+ * end_bit beyond the key's width is CL_E_INVALID.  d_vals may be null in cl_sort_u32_u32 (keys only). */
+cl_status cl_sort_u32(cl_ctx* ctx, uint32_t* d_keys, uint64_t n, uint32_t begin_bit, uint32_t end_bit);
+cl_status cl_sort_u32_u32(cl_ctx* ctx, uint32_t* d_keys, uint32_t* d_vals, uint64_t n, uint32_t begin_bit, uint32_t end_bit);
+/* The same sorts in the form the coders call: on pool buffers of exactly n elements that may come back exchanged with the sort's
+ * temporaries instead of being copied into.  The input arrays are left as they are; the result goes to d_keys_out / d_vals_out. */
+cl_status cl_sort_swap_u32_u32(cl_ctx* ctx, const uint32_t* d_keys_in, const uint32_t* d_vals_in, uint64_t n, uint32_t begin_bit, uint32_t end_bit,
+                               uint32_t* d_keys_out, uint32_t* d_vals_out);
+cl_status cl_sort_swap_u64_u32(cl_ctx* ctx, const uint64_t* d_keys_in, const uint32_t* d_vals_in, uint64_t n, uint32_t begin_bit, uint32_t end_bit,
+                               uint64_t* d_keys_out, uint32_t* d_vals_out);
+/* In-place exclusive prefix sums of n uint32; *h_total (optional) = the sum.  With h_total a sum of 2^32 or more is refused
+ * (CL_E_UNSUPPORTED; the array then holds meaningless prefixes); without it nothing is checked. */
+cl_status cl_scan_u32(cl_ctx* ctx, uint32_t* d_data, uint64_t n, uint64_t* h_total);
+/* d_out[0 .. n] = exclusive prefix sums of d_in[0 .. n) in 64 bits, d_out[n] = *h_total (optional) = the sum.  With h_total a sum of
+ * 2^52 - 1 or more is refused (CL_E_UNSUPPORTED). */
+cl_status cl_scan_u32_u64(cl_ctx* ctx, const uint32_t* d_in, uint64_t* d_out, uint64_t n, uint64_t* h_total);
+/* Starts of the runs of equal `key >> shift` in sorted keys: d_seg[0 .. r) = first positions, d_seg[r] = n, *h_n_runs = r.  seg_cap
+ * (elements of d_seg) MUST exceed r — the caller bounds it by n and by the distinct values of key >> shift; the kernel has written by
+ * the time CL_E_CAPACITY is returned.  shift at or beyond the key's width is CL_E_INVALID, n >= 2^32 CL_E_UNSUPPORTED. */
+cl_status cl_run_starts_u32(cl_ctx* ctx, const uint32_t* d_keys, uint64_t n, uint32_t shift, uint32_t* d_seg, uint64_t seg_cap, uint64_t* h_n_runs);
+cl_status cl_run_starts_u64(cl_ctx* ctx, const uint64_t* d_keys, uint64_t n, uint32_t shift, uint32_t* d_seg, uint64_t seg_cap, uint64_t* h_n_runs);
 
 #ifdef __cplusplus
 }
