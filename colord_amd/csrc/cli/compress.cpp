@@ -200,6 +200,11 @@ int run_compress(int argc, char** argv)
 	if (O.verify_streams) cl_ctx_set_verify_streams(ctx, 1);
 	if (O.digest) cl_ctx_set_digest(ctx, 1);
 	ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, nullptr, estimated_bases(R), &cmp), "cl_compressor_create");
+	if (O.qual_domain_symbols)
+	{
+		if (!with_qual) die("--qual-domain-symbols needs a quality stream (the input has none)");
+		ck(ctx, cl_compressor_set_qual_domain_symbols(cmp, O.qual_domain_symbols), "cl_compressor_set_qual_domain_symbols");
+	}
 	GenomeMode GM;
 	if (!O.genome.empty()) { GM.read(O); GM.count_kmers(ctx, cmp); }
 	// pass 1 while parsing: every chunk goes to HBM (2-bit arena + quality bytes) and stays there for the three passes.
@@ -264,6 +269,7 @@ int run_compress(int argc, char** argv)
 	if (s_genome >= 0) GM.store(ar, s_genome);
 	// pass 2: chunk by chunk; the parts of a chunk go to the archive (PartWriter) while the next chunk is coded
 	uint64_t dna_total = 0, qual_total = 0; uint32_t n_parts_total = 0;
+	std::vector<uint64_t> part_first_read; uint64_t reads_before = 0;       // (--qual-domain-symbols: the first read of every part of the file)
 	PartWriter pw(ar, s_dna, s_qual, chunks, O.stream_input ? nullptr : pipe.buf);
 	std::unique_ptr<ChunkLoader> loader; if (O.stream_input) loader = std::make_unique<ChunkLoader>(O.gpu, pipe, chunks, with_qual, up.cache);
 	const size_t ann_window = announce_window();
@@ -282,6 +288,8 @@ int run_compress(int argc, char** argv)
 		t_encode += std::chrono::duration<double>(std::chrono::steady_clock::now() - te).count();
 		pw.submit(ci, std::move(dsz), std::move(qsz), info);
 		dna_total += info.dna_bytes; qual_total += info.qual_bytes; n_parts_total += np;
+		for (uint32_t p = 0; p < np; ++p) part_first_read.push_back(reads_before + dc.parts[p]);
+		reads_before += dc.n_reads;
 		// (a resident chunk stays where it is until the pass is over: hipFree waits for the whole device — the lanes and the preparation
 		// working ahead on the next chunks — and nobody needs the room)
 		if (O.stream_input) loader->coded(ci);                                                                                // (the loader releases it)
@@ -310,6 +318,15 @@ int run_compress(int argc, char** argv)
 		ck(ctx, cl_compressor_digest(cmp, &dd, &dq), "cl_compressor_digest");
 		if (dd.reads != n || dd.symbols != total) die("internal: the content digest did not see every read");
 		add_digest(ar, dd, with_qual && O.P.qual_mode != 8 ? &dq : nullptr, hdr.digest);
+	}
+	if (O.qual_domain_symbols)
+	{
+		uint64_t nd = 0;
+		(void)cl_compressor_qual_domains(cmp, nullptr, 0, &nd);
+		std::vector<uint64_t> first(nd);
+		ck(ctx, cl_compressor_qual_domains(cmp, first.data(), nd, &nd), "cl_compressor_qual_domains");
+		add_qual_domains(ar, first, part_first_read);
+		if (O.verbose) fprintf(stderr, "# quality model domains: %llu (of %llu symbols or more each but the last)\n", (unsigned long long)nd, (unsigned long long)O.qual_domain_symbols);
 	}
 	finish_archive(ar, O, R, tot);
 	gzclose(R.g);

@@ -295,6 +295,17 @@ inline void add_digest(ArchiveWriter& ar, const cl_digest& dna, const cl_digest*
 	const std::vector<uint8_t> b = S.pack();
 	ar.add(ar.reg("hipdigest"), b.data(), b.size(), 0);
 }
+// `hipqdomains` (--qual-domain-symbols): u64 count, then per model domain of the quality stream its first `qual` part and its first read
+inline void add_qual_domains(ArchiveWriter& ar, const std::vector<uint64_t>& first_part, const std::vector<uint64_t>& part_first_read)
+{
+	std::vector<uint8_t> b; le<uint64_t>(b, first_part.size());
+	for (uint64_t p : first_part)
+	{
+		if (p >= part_first_read.size()) die("internal: a quality model domain starts behind the last part");
+		le<uint64_t>(b, p); le<uint64_t>(b, part_first_read[p]);
+	}
+	ar.add(ar.reg("hipqdomains"), b.data(), b.size(), 0);
+}
 inline void finish_archive(ArchiveWriter& ar, const Options& O, const Reader& R, const Totals& T)
 {
 	std::vector<uint8_t> inf;

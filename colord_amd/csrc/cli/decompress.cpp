@@ -4,10 +4,106 @@
 // archive has no `qual` stream.  No GPU is needed to decompress.  An archive with a `hipdigest` stream (digest_stream.hpp) is checked
 // against it while it is decoded; `check` decodes without writing and prints the digests.
 #include "reader.hpp"
+#include <hip/hip_runtime.h>
+#include <chrono>
 #include <ctime>
 #include <memory>
 #include <algorithm>
 using namespace colord_hip_reader;
+
+// the device number of `--gpu N`: digits only
+static int gpu_number(const char* v)
+{
+	char* end = nullptr; const long g = strtol(v, &end, 10);
+	if (!*v || *end || v[0] < '0' || v[0] > '9' || g < 0 || g > 1023) die(std::string("--gpu needs a device number, not '") + v + "'");
+	return (int)g;
+}
+
+// ---- `--gpu N`: the quality stream of an archive with `hipqdomains` decoded on the device -----------------------------------------------
+// A batch of whole model domains (reader.hpp collects them behind the DNA thread): the bases go to the device and are packed into an arena
+// (cl_reads_pack), the class flags of levels 2 and 3 into the form of cl_es_flags, the payloads back to back; cl_qual_decode_domains decodes
+// one domain per lane; the qualities come back into the parts, the symbols (for the content digest) through cl_digest_bytes_host.  Without
+// --gpu nothing here runs and no device is initialised.
+namespace {
+struct DevMem {
+	void* p = nullptr;
+	explicit DevMem(uint64_t bytes) { if (hipMalloc(&p, std::max<uint64_t>(bytes, 16)) != hipSuccess) { (void)hipGetLastError(); p = nullptr; throw std::runtime_error("device memory for the quality decoder (" + std::to_string(bytes) + " bytes)"); } }
+	~DevMem() { if (p) (void)hipFree(p); }
+	DevMem(const DevMem&) = delete; DevMem& operator=(const DevMem&) = delete;
+	template<class T> T* as() const { return (T*)p; }
+	void put(const void* h, uint64_t bytes) { if (bytes && hipMemcpy(p, h, bytes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("copy to the device"); }
+	void get(void* h, uint64_t bytes) const { if (bytes && hipMemcpy(h, p, bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("copy from the device"); }
+};
+struct DeviceQualDecoder {
+	int gpu = 0; cl_ctx* ctx = nullptr;
+	uint64_t batches = 0, domains = 0, max_domains = 0, symbols = 0; double seconds = 0, call_seconds = 0, lane_symbol_seconds = 0;       // (the line on stderr at the end)
+	explicit DeviceQualDecoder(int g) : gpu(g) {}
+	~DeviceQualDecoder() { if (ctx) cl_ctx_destroy(ctx); }
+	void operator()(const cl_qual_params& meta_params, QualBatch& B, cl_digest* acc)
+	{
+		if (!ctx && (hipSetDevice(gpu) != hipSuccess || cl_ctx_create(gpu, &ctx) != CL_OK)) { ctx = nullptr; throw std::runtime_error("--gpu " + std::to_string(gpu) + ": no such device"); }
+		const auto t0 = std::chrono::steady_clock::now();
+		cl_qual_params qp = meta_params;
+		const uint32_t n_parts = (uint32_t)B.parts.size(), n_reads = (uint32_t)B.n_reads;
+		// the batch as one read set: offsets, base codes (class flags taken off), flags, part bounds, payloads
+		std::vector<uint64_t> off; off.reserve((size_t)n_reads + 1); off.push_back(0);
+		std::vector<uint32_t> bounds(1, 0); std::vector<uint64_t> sizes; uint64_t n_in = 0;
+		std::vector<uint8_t> codes(B.n_bases), flags(qp.level > 1 ? B.n_bases : 0);
+		uint64_t o = 0;
+		for (uint32_t p = 0; p < n_parts; ++p)
+		{
+			const ReadPart& x = B.parts[p];
+			for (size_t r = 0; r + 1 < x.off.size(); ++r) off.push_back(o + x.off[r + 1]);
+			for (size_t i = 0; i < x.bases.size(); ++i)
+			{
+				const uint8_t b = x.bases[i];
+				codes[o + i] = (b & 7) > 4 ? 4 : (b & 7);
+				if (qp.level > 1) flags[o + i] = (b & 0x80) ? 'A' : (b & 0x40) ? 'M' : ' ';               // basic_coder.h:34-35 -> the classes of cl_es_flags
+			}
+			o += x.bases.size();
+			bounds.push_back((uint32_t)(off.size() - 1));
+			sizes.push_back(B.payloads[p].size()); n_in += B.payloads[p].size();
+		}
+		if (off.size() - 1 != n_reads || o != B.n_bases) throw std::runtime_error("the batch's counts do not fit its parts");
+		static const uint32_t NAVG[9] = { 0, 10, 8, 4, 0, 0, 0, 2, 0 };
+		const uint32_t navg = NAVG[qp.mode]; const bool per_base = qp.mode <= 6, want_symbols = acc && qp.mode != 8;
+		const uint64_t n_syms = (uint64_t)n_reads * navg + (per_base ? B.n_bases : 0);
+		DevMem d_codes(B.n_bases), d_off(((uint64_t)n_reads + 1) * 8), d_flags(flags.size()), d_in(n_in), d_quals(B.n_bases), d_syms(want_symbols ? n_syms : 0);
+		d_codes.put(codes.data(), B.n_bases); d_off.put(off.data(), off.size() * 8); d_flags.put(flags.data(), flags.size());
+		{ uint64_t at = 0; for (uint32_t p = 0; p < n_parts; ++p) { if (hipMemcpy(d_in.as<uint8_t>() + at, B.payloads[p].data(), sizes[p], hipMemcpyHostToDevice) != hipSuccess && sizes[p]) throw std::runtime_error("copy to the device"); at += sizes[p]; } }
+		cl_reads* reads = nullptr;
+		if (cl_reads_pack(ctx, d_codes.as<uint8_t>(), d_off.as<uint64_t>(), n_reads, 0, &reads) != CL_OK) throw std::runtime_error(std::string("cl_reads_pack: ") + cl_last_error(ctx));
+		const auto tc = std::chrono::steady_clock::now();
+		const cl_status s = cl_qual_decode_domains(ctx, &qp, reads, qp.level > 1 ? d_flags.as<uint8_t>() : nullptr, d_in.as<uint8_t>(), n_in, bounds.data(), sizes.data(), n_parts,
+		                                           B.domain_first.data(), (uint32_t)B.domain_first.size(), 0, d_quals.as<uint8_t>(), d_off.as<uint64_t>(), B.n_bases, want_symbols ? d_syms.as<uint8_t>() : nullptr, want_symbols ? n_syms : 0);
+		const double t_call = std::chrono::duration<double>(std::chrono::steady_clock::now() - tc).count();
+		cl_reads_free(reads);
+		if (s != CL_OK) throw std::runtime_error(cl_last_error(ctx));
+		call_seconds += t_call; lane_symbol_seconds += t_call * (double)B.domain_first.size();      // (lanes x seconds, batch by batch: the widths differ)
+		std::vector<uint8_t> quals(B.n_bases);
+		d_quals.get(quals.data(), B.n_bases);
+		o = 0;
+		for (ReadPart& x : B.parts) { x.quals.assign(quals.begin() + o, quals.begin() + o + x.bases.size()); o += x.bases.size(); }
+		if (want_symbols)
+		{
+			std::vector<uint8_t> syms(n_syms); std::vector<uint64_t> so((size_t)n_reads + 1);
+			d_syms.get(syms.data(), n_syms);
+			for (uint64_t r = 0; r <= n_reads; ++r) so[r] = r * navg + (per_base ? off[r] : 0);
+			if (cl_digest_bytes_host(2, syms.data(), so.data(), n_reads, B.first_read, acc) != CL_OK) throw std::runtime_error("more reads than the content digest can index");
+		}
+		++batches; domains += B.domain_first.size(); max_domains = std::max<uint64_t>(max_domains, B.domain_first.size()); symbols += n_syms;
+		seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+	}
+	void report() const
+	{
+		if (!batches) return;
+		// per lane: a batch's symbols over its lanes x the seconds of its cl_qual_decode_domains call (table set-up, launches and the wait for
+		// them; the longest domain of a launch sets its time) — not the packing and the copies around it, which `in all` includes
+		fprintf(stderr, "colord_hip: quality stream decoded on GPU %d: %llu model domains in %llu batch(es), at most %llu in flight; %llu symbols, %.2f s in the decode calls (%.0f symbols/s per lane), %.2f s in all with packing and copies\n",
+			gpu, (unsigned long long)domains, (unsigned long long)batches, (unsigned long long)max_domains, (unsigned long long)symbols, call_seconds, lane_symbol_seconds > 0 ? (double)symbols / lane_symbol_seconds : 0.0, seconds);
+	}
+};
+} // namespace
 
 int run_info(int argc, char** argv)
 {
@@ -113,15 +209,28 @@ static bool decode_domains(const std::string& arc, const std::string& genome, co
 
 // The records of an archive in file order, written to out_path (empty: decoded only).  remove_on_error: a decoding error takes the
 // output file with it (an archive whose content digest is being checked leaves no half-written or unconfirmed file behind).
-static void decode_archive(const std::string& arc, const std::string& genome, const std::string& out_path, int dom_threads, bool want_digest, bool remove_on_error, Decoded& D)
+// gpu >= 0 (`--gpu N`): the quality stream of an archive with `hipqdomains` is decoded on that device; any other archive on the host as ever
+static void decode_archive(const std::string& arc, const std::string& genome, const std::string& out_path, int dom_threads, bool want_digest, bool remove_on_error, int gpu, Decoded& D)
 {
 	auto fail = [&](const std::string& m) { if (remove_on_error && !out_path.empty()) (void)remove(out_path.c_str()); die(m); };
-	try { if (decode_domains(arc, genome, out_path, dom_threads, want_digest, D)) return; } catch (const std::exception& e) { fail(e.what()); }
+	const char* why_host = "--gpu: the archive has no `hipqdomains` stream (it was written without --qual-domain-symbols): its quality stream is one dependent chain per domain and is decoded on the host";
+	try { if (decode_domains(arc, genome, out_path, dom_threads, want_digest, D)) { if (gpu >= 0) fprintf(stderr, "colord_hip: %s\n", why_host); return; } } catch (const std::exception& e) { fail(e.what()); }
 	bool write_ok = true;
+	DeviceQualDecoder dev(gpu);                                                // (outlives the record stream, whose quality thread calls it)
 	try
 	{
 		RecordStream rs(arc, genome);
 		if (want_digest) rs.enable_digest();
+		if (gpu >= 0)
+		{
+			if (rs.n_qual_domains())
+			{
+				uint64_t max_bases = 1ull << 30;
+				if (const char* e = getenv("COLORD_HIP_QDEC_BATCH_BASES")) max_bases = strtoull(e, nullptr, 10);
+				rs.set_qual_batch_decoder(std::ref(dev), max_bases);
+			}
+			else fprintf(stderr, "colord_hip: %s\n", why_host);
+		}
 		FILE* out = out_path.empty() ? nullptr : fopen(out_path.c_str(), "wb");
 		if (!out_path.empty() && !out) die("cannot open file: " + out_path);
 		std::vector<char> obuf(out ? 1 << 24 : 1); if (out) setvbuf(out, obuf.data(), _IOFBF, obuf.size());
@@ -140,6 +249,7 @@ static void decode_archive(const std::string& arc, const std::string& genome, co
 		if (out && (fflush(out) != 0 || ferror(out))) write_ok = false;
 		if (out && fclose(out) != 0) write_ok = false;
 		if (want_digest && write_ok) D.computed = rs.digests();
+		dev.report();
 	}
 	catch (const std::exception& e) { fail(e.what()); }
 	if (!write_ok) fail("cannot write " + out_path + " (disk full?)");
@@ -148,22 +258,23 @@ static void decode_archive(const std::string& arc, const std::string& genome, co
 int run_decompress(int argc, char** argv)
 {
 	std::vector<std::string> pos; std::string genome; int dom_threads = (int)std::min<unsigned>(16, std::max<unsigned>(1, std::thread::hardware_concurrency() / 3));
-	bool ignore_digest = false;
+	bool ignore_digest = false; int gpu = -1;
 	for (int i = 2; i < argc; ++i)
 	{
 		const std::string a = argv[i];
 		if ((a == "-G" || a == "--reference-genome") && i + 1 < argc) genome = argv[++i];      // needed when the archive was written with -G but without -s
+		else if (a == "--gpu" && i + 1 < argc) gpu = gpu_number(argv[++i]);
 		else if (a == "-v" || a == "--verbose") ;
 		else if ((a == "-t" || a == "--threads") && i + 1 < argc) dom_threads = atoi(argv[++i]);
 		else if (a == "--ignore-digest") ignore_digest = true;                                  // salvage: decode whatever the stored content digest says
 		else pos.push_back(a);
 	}
-	if (pos.size() != 2) { fprintf(stderr, "usage: colord_hip decompress [-G reference_genome.fa] [--ignore-digest] archive.colord output.fastq\n"); return 1; }
+	if (pos.size() != 2) { fprintf(stderr, "usage: colord_hip decompress [-G reference_genome.fa] [--ignore-digest] [--gpu N] archive.colord output.fastq\n"); return 1; }
 	// an archive written with --digest is checked while it is decoded: the stream threads digest what they decode
 	DigestSet stored; const int have = ignore_digest ? 0 : read_hipdigest(pos[0], stored);
 	if (have < 0) die("the archive's `hipdigest` stream is not one this build reads (--ignore-digest decodes without the check)");
 	Decoded D;
-	decode_archive(pos[0], genome, pos[1], dom_threads, have > 0, have > 0, D);
+	decode_archive(pos[0], genome, pos[1], dom_threads, have > 0, have > 0, gpu, D);
 	if (have > 0)
 	{
 		const std::string bad = digest_mismatch(stored, D.computed);
@@ -180,17 +291,19 @@ int run_decompress(int argc, char** argv)
 int run_check(int argc, char** argv)
 {
 	std::vector<std::string> pos; std::string genome; int dom_threads = (int)std::min<unsigned>(16, std::max<unsigned>(1, std::thread::hardware_concurrency() / 3));
+	int gpu = -1;
 	for (int i = 2; i < argc; ++i)
 	{
 		const std::string a = argv[i];
 		if ((a == "-G" || a == "--reference-genome") && i + 1 < argc) genome = argv[++i];
+		else if (a == "--gpu" && i + 1 < argc) gpu = gpu_number(argv[++i]);
 		else if ((a == "-t" || a == "--threads") && i + 1 < argc) dom_threads = atoi(argv[++i]);
 		else pos.push_back(a);
 	}
-	if (pos.size() != 1) { fprintf(stderr, "usage: colord_hip check [-G reference_genome.fa] archive.colord\n"); return 1; }
+	if (pos.size() != 1) { fprintf(stderr, "usage: colord_hip check [-G reference_genome.fa] [--gpu N] archive.colord\n"); return 1; }
 	DigestSet stored; const int have = read_hipdigest(pos[0], stored);
 	Decoded D;
-	decode_archive(pos[0], genome, "", dom_threads, true, false, D);
+	decode_archive(pos[0], genome, "", dom_threads, true, false, gpu, D);
 	for (int i = 0; i < 3; ++i) printf("%s\n", D.computed.line(i).c_str());
 	if (have == 0) { printf("no content digest is stored in this archive (written without --digest); %llu records decode\n", (unsigned long long)D.n_rec); return 0; }
 	if (have < 0) { printf("the archive's `hipdigest` stream is not one this build reads\n"); return 1; }

@@ -38,6 +38,7 @@ struct Options {
 	bool verify_scripts = false;                    // --verify-scripts: cl_ctx_set_verify on every compressor's context
 	bool verify_streams = false;                    // --verify-streams: cl_ctx_set_verify_streams on every compressor's context
 	bool digest = false;                            // --digest: content digests of the input (cl_ctx_set_digest; ids on the host) in a `hipdigest` stream
+	uint64_t qual_domain_symbols = 0;               // --qual-domain-symbols N: the quality models start afresh about every N symbols (cl_compressor_set_qual_domain_symbols; stream `hipqdomains`)
 	int gpus = 1; std::vector<int> gpu_list; std::string transport = "rccl";   // --gpus N [--gpu-list a,b,..] [--transport rccl|host]: reads sharded over N GPUs (run_compress_multi)
 	Preset P{}; QDef qd;                            // resolved by parse_options: the preset of source and priority with the options laid over it, the quality thresholds / representatives
 	int argc = 0; char** argv = nullptr;            // the command line as given (`info` stream)
@@ -47,7 +48,7 @@ inline void usage()
 {
 	fprintf(stderr,
 		"usage: colord_hip compress-ont|compress-pbhifi|compress-pbraw [options] input.fastq|fasta[.gz] output.colord\n"
-		"       colord_hip decompress [--ignore-digest] archive.colord output.fastq\n       colord_hip check archive.colord\n       colord_hip info archive.colord\n"
+		"       colord_hip decompress [--ignore-digest] [--gpu N] archive.colord output.fastq\n       colord_hip check [--gpu N] archive.colord\n       colord_hip info archive.colord\n"
 		"options (as the reference, arg_parse.cpp:455-640):\n"
 		"  -p,--priority ratio|balanced|memory   -k,--kmer-len K with -a,--anchor-len A (both or none)\n"
 		"  -q,--qual org|none|avg|2-fix|4-fix|5-fix|2-avg|4-avg|5-avg   -T,--qual-thresholds a,b,..   -D,--qual-values a,b,..\n"
@@ -70,6 +71,12 @@ inline void usage()
 		"                     decodes: a difference is a message naming the stream, no output file and exit 1 (--ignore-digest decodes regardless); `colord_hip check` decodes without\n"
 		"                     writing and prints them.  Same digest with any --part-symbols, --stream-input, --domains, --gpus.  Covered: input -> ... -> decoded symbols; the quality\n"
 		"                     VALUES made from the symbols (-D values, error diffusion of *-avg) are not.  Cost: one pass over 1.4 bytes per base per chunk (not measured on a GPU yet)\n"
+		"  --qual-domain-symbols N   model domains of the QUALITY stream alone: its adaptive models start afresh at the first part boundary at which a domain holds N coded\n"
+		"                     symbols, and the starts are recorded (stream `hipqdomains`).  `colord_hip decompress --gpu N` / `check --gpu N` then decode the domains side by\n"
+		"                     side on the device, one lane each; without --gpu they decode on the host as one chain that starts afresh at every domain.  The k-mer set, the\n"
+		"                     reference reads and the `dna`, `header` and `hipdigest` streams are untouched.  The reference's decompressor CANNOT read such an archive: it\n"
+		"                     ignores the stream and carries its models on.  Costs `qual` bytes per domain (the models relearn; NOT measured yet — no size table exists, DESIGN.md 9 has the protocol).  Not with --gpus > 1,\n"
+		"                     --domains > 1 or -q none\n"
 		"  --domains K        K independent model domains (equal shares of the reads, each compressed on its own): `colord_hip decompress`\n"
 		"                     decodes them side by side; costs archive size (own k-mer statistics and reference reads per domain)\n"
 		"  --gpus N [--gpu-list a,b,..] [--transport rccl|host]   reads sharded over N GPUs, one host thread and one model domain per GPU;\n"
@@ -123,6 +130,7 @@ inline Options parse_options(int argc, char** argv)
 		else if (a == "--transport") { O.transport = need(i); if (O.transport != "rccl" && O.transport != "host") die("--transport must be rccl or host"); }
 		else if (a == "--chunk-bases") { O.chunk_bases = atof(need(i).c_str()); O.chunk_bases_set = true; }
 		else if (a == "--part-symbols") { O.part_symbols = strtoull(need(i).c_str(), nullptr, 10); if (O.part_symbols < 1024 || O.part_symbols > (2u << 21)) die("--part-symbols must be in [1024, 4194304]"); }
+		else if (a == "--qual-domain-symbols") { O.qual_domain_symbols = strtoull(need(i).c_str(), nullptr, 10); if (O.qual_domain_symbols < 1) die("--qual-domain-symbols must be positive"); }
 		else if (a == "--stream-input") O.stream_input = true;
 		else if (a == "--verify-scripts") O.verify_scripts = true;
 		else if (a == "--verify-streams") O.verify_streams = true;
@@ -154,5 +162,11 @@ inline Options parse_options(int argc, char** argv)
 	if (!O.gpu_list.empty() && O.gpus == 1) O.gpus = (int)O.gpu_list.size();
 	if (O.domains > 1 && O.gpus > 1) die("--domains and --gpus exclude each other (every GPU is a model domain already)");
 	if (O.stream_input && O.domains > 1) die("--stream-input is not available with --domains");
+	if (O.qual_domain_symbols)
+	{
+		if (O.gpus > 1) die("--qual-domain-symbols is not available with --gpus > 1 (every GPU is a model domain already)");
+		if (O.domains > 1) die("--qual-domain-symbols is not available with --domains > 1");
+		if (P.qual_mode == 8) die("--qual-domain-symbols needs a coded quality stream: not with -q none (the default of compress-pbraw)");
+	}
 	return O;
 }

@@ -6,7 +6,9 @@
 // Three host threads decode the `dna`, `qual` and `header` streams part by part (the quality decoder consumes the bases the DNA
 // decoder produced for the same part, entr_qual.h:136-260); next() hands out the records in file order.  Archives written by
 // several GPUs carry a `hipdomains` stream: the first `dna` part of every model domain, where both coders start from fresh
-// models.  No GPU is needed.  Errors are std::runtime_error (the command-line tool turns them into its exit message).
+// models; archives written with --qual-domain-symbols a `hipqdomains` stream: the first `qual` part of every model domain of the
+// quality stream alone (fresh quality models there; a caller may have whole domains decoded many at a time: set_qual_batch_decoder,
+// which `colord_hip decompress --gpu` uses for the device).  No GPU is needed.  Errors are std::runtime_error (the command-line tool turns them into its exit message).
 #pragma once
 #include "colord_hip.h"
 #include "archive.hpp"
@@ -14,8 +16,10 @@
 #include "digest_stream.hpp"
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <mutex>
 #include <stdexcept>
+#include <algorithm>
 #include <thread>
 
 #include <ctime>
@@ -29,11 +33,13 @@ static inline void thread_report(const char* what)
 
 namespace colord_hip_reader {
 template<class T> struct Queue {                                       // bounded hand-over between the stream threads
-	std::mutex m; std::condition_variable cv; std::deque<T> q; bool done = false; size_t cap = 4;
-	void push(T&& v) { std::unique_lock<std::mutex> l(m); cv.wait(l, [&] { return q.size() < cap || done; }); if (done) return; q.push_back(std::move(v)); cv.notify_all(); }
-	bool pop(T& v) { std::unique_lock<std::mutex> l(m); cv.wait(l, [&] { return !q.empty() || done; }); if (q.empty()) return false; v = std::move(q.front()); q.pop_front(); cv.notify_all(); return true; }
+	// bounded by the number of items (cap) and, where weight_cap is set, by their summed weights (bases): a push waits while the queue
+	// holds weight_cap or more (an item heavier than the bound still passes through an empty queue)
+	std::mutex m; std::condition_variable cv; std::deque<T> q; std::deque<uint64_t> wq; bool done = false; size_t cap = 4; uint64_t weight_cap = 0, weight = 0;
+	void push(T&& v, uint64_t w = 0) { std::unique_lock<std::mutex> l(m); cv.wait(l, [&] { return (q.size() < cap && !(weight_cap && weight >= weight_cap && !q.empty())) || done; }); if (done) return; q.push_back(std::move(v)); wq.push_back(w); weight += w; cv.notify_all(); }
+	bool pop(T& v) { std::unique_lock<std::mutex> l(m); cv.wait(l, [&] { return !q.empty() || done; }); if (q.empty()) return false; v = std::move(q.front()); q.pop_front(); weight -= wq.front(); wq.pop_front(); cv.notify_all(); return true; }
 	void finish() { std::unique_lock<std::mutex> l(m); done = true; cv.notify_all(); }
-	void abort() { std::unique_lock<std::mutex> l(m); done = true; q.clear(); cv.notify_all(); }          // the consumer goes away: producers must not block
+	void abort() { std::unique_lock<std::mutex> l(m); done = true; q.clear(); wq.clear(); weight = 0; cv.notify_all(); }          // the consumer goes away: producers must not block
 };
 struct ReadPart { std::vector<uint8_t> bases; std::vector<uint64_t> off; std::vector<uint8_t> quals; };
 struct HeaderPart { std::vector<uint8_t> ids; std::vector<uint64_t> off; std::vector<uint8_t> plus; };
@@ -47,7 +53,7 @@ struct ArchiveInfo {                                                   // the `i
 	uint32_t version_major = 0, version_minor = 0, version_patch = 0; uint64_t total_bytes = 0, total_bases = 0; uint32_t total_reads = 0; uint64_t time = 0;
 	std::string command_line;
 };
-template<class T> T rd(const uint8_t*& p, const uint8_t* e) { if (p + sizeof(T) > e) throw std::runtime_error("truncated stream in the archive"); T v; memcpy(&v, p, sizeof(T)); p += sizeof(T); return v; }
+template<class T> T rd(const uint8_t*& p, const uint8_t* e) { if ((size_t)(e - p) < sizeof(T)) throw std::runtime_error("truncated stream in the archive"); T v; memcpy(&v, p, sizeof(T)); p += sizeof(T); return v; }
 inline Meta parse_meta(const std::vector<uint8_t>& b, bool is_fastq)         // decompression_common.cpp:51-265
 {
 	Meta m; const uint8_t* p = b.data(); const uint8_t* e = p + b.size();
@@ -78,6 +84,37 @@ inline ArchiveInfo parse_info(const std::vector<uint8_t>& b)
 	I.command_line.assign((const char*)p, (const char*)p + std::min<size_t>(cl, (size_t)(e - p)));
 	return I;
 }
+
+// Model domains of the QUALITY stream alone (`hipqdomains`, written by `colord_hip compress-* --qual-domain-symbols`): u64 count, then per
+// domain its first `qual` part and its first read.  The quality models start afresh at every one of them (cl_qual_decoder_new_domain on the
+// host; cl_qual_decode_domains decodes them side by side on the device); nothing else does.  The first domain starts with the stream.
+// The first reads are a cross-check: a decoder counts the reads of the parts itself, and a domain that does not start at the read the
+// stream names is a corrupt archive (check_qdomain_read).
+struct QualDomain { uint64_t first_part, first_read; };
+inline std::vector<QualDomain> parse_qdomains(const std::vector<uint8_t>& b, uint64_t n_parts)
+{
+	const uint8_t* p = b.data(); const uint8_t* e = p + b.size();
+	const uint64_t n = rd<uint64_t>(p, e);
+	if (n == 0 || n > (uint64_t)(e - p) / 16 || (uint64_t)(e - p) != n * 16) throw std::runtime_error("corrupt `hipqdomains` stream: its size does not fit its count");
+	std::vector<QualDomain> v; v.reserve(n);
+	for (uint64_t i = 0; i < n; ++i)
+	{
+		QualDomain d; d.first_part = rd<uint64_t>(p, e); d.first_read = rd<uint64_t>(p, e);
+		const bool ok = i == 0 ? (d.first_part == 0 && d.first_read == 0) : (d.first_part > v.back().first_part && d.first_read >= v.back().first_read);
+		if (!ok || d.first_part >= n_parts) throw std::runtime_error("corrupt `hipqdomains` stream: domain " + std::to_string(i) + " does not start where a domain can");
+		v.push_back(d);
+	}
+	return v;
+}
+// Whole model domains of the quality stream on their way to a decoder that takes many at once (the device: cli/decompress.cpp): the parts'
+// bases and offsets as the DNA decoder left them, their payloads, and where the domains start.  The decoder fills every part's `quals`.
+struct QualBatch {
+	std::vector<ReadPart> parts; std::vector<std::vector<uint8_t>> payloads;
+	std::vector<uint32_t> domain_first;                                    // the first part of every domain, counted in this batch (the first is 0)
+	uint64_t first_read = 0, n_reads = 0, n_bases = 0;                     // the batch's first read in the whole input; its reads and bases
+};
+// throws std::runtime_error where the batch does not decode; acc (null: not wanted): the qual digest of the batch's reads is added
+using QualBatchDecoder = std::function<void(const cl_qual_params&, QualBatch&, cl_digest* acc)>;
 
 struct Record { const uint8_t* header; size_t header_len; const uint8_t* bases; size_t n_bases; const uint8_t* quals; bool plus_is_header; };   // views, valid until the next call
 
@@ -127,6 +164,15 @@ class RecordStream {
 	// so it is decoded by a DNA decoder of its own (with its own sparse range) — and K of them side by side (cli/decompress.cpp)
 	bool independent = false; std::vector<uint64_t> dom_part{ 0 }, dom_read{ 0 }; std::vector<uint32_t> dom_sparse;
 	int only_domain = -1; const HeaderCache* ext_hdr = nullptr; uint64_t read_index = 0;
+	std::vector<QualDomain> qdomains;                                      // `hipqdomains`: the model domains of the quality stream alone (empty: none)
+	QualBatchDecoder qual_batches; uint64_t qual_batch_bases = 1ull << 30;  // set_qual_batch_decoder
+	void check_qdomain_read(size_t part, uint64_t reads_before) const
+	{
+		const auto it = std::lower_bound(qdomains.begin(), qdomains.end(), QualDomain{ part, 0 }, [](const QualDomain& a, const QualDomain& b) { return a.first_part < b.first_part; });
+		if (it != qdomains.end() && it->first_part == part && it->first_read != reads_before)
+			throw std::runtime_error("corrupt `hipqdomains` stream: the domain at part " + std::to_string(part) + " is said to start at read " + std::to_string(it->first_read) + ", the parts before it hold " + std::to_string(reads_before));
+	}
+	bool is_qdomain_start(size_t part) const { return std::binary_search(qdomains.begin(), qdomains.end(), QualDomain{ part, 0 }, [](const QualDomain& a, const QualDomain& b) { return a.first_part < b.first_part; }); }
 	// content digest (digest_stream.hpp): each stream thread digests what it decodes, read by read from the first read it decodes on
 	bool want_digest = false; cl_digest dig_dna{ 0, 0, 0 }, dig_qual{ 0, 0, 0 }, dig_hdr{ 0, 0, 0 };
 	uint64_t first_read_index() const { return only_domain >= 0 ? dom_read[only_domain] : 0; }
@@ -152,6 +198,13 @@ public:
 	// dna, qual (flag off without a quality stream or in mode none, which decodes nothing) and header (not with external ids: theirs is the cache's)
 	void enable_digest() { if (!started) want_digest = true; }
 	DigestSet digests() const { DigestSet s; s.flags = 1u | (fastq && M.qual_mode != 8 ? 2u : 0u) | (ext_hdr ? 0u : 4u); s.d[0] = dig_dna; s.d[1] = dig_qual; s.d[2] = dig_hdr; return s; }
+	// `hipqdomains`: how many model domains the quality stream has of its own (0: none — one chain, or the domains of `hipdomains`)
+	size_t n_qual_domains() const { return qdomains.size(); }
+	// before the first record is asked for, archives with `hipqdomains` only: the quality thread no longer decodes part by part — it
+	// collects whole domains behind the DNA thread (bases, flags, payloads) until they hold max_bases bases or the stream ends, hands
+	// each batch to `fn` and passes the qualities on in file order.  The DNA thread runs ahead meanwhile: the queues between the
+	// threads are unbounded then (a batch's bases are resident anyway).
+	void set_qual_batch_decoder(QualBatchDecoder fn, uint64_t max_bases = 1ull << 30) { if (!started && !qdomains.empty()) { qual_batches = std::move(fn); qual_batch_bases = std::max<uint64_t>(1, max_bases); } }
 	void prefetch() { if (!started) start(); }                           // starts the decoder threads before the first next()
 	~RecordStream() { q_bases_for_qual.abort(); q_reads.abort(); q_quals.abort(); q_hdr.abort(); join(); ar.close(); }
 	RecordStream(const RecordStream&) = delete; RecordStream& operator=(const RecordStream&) = delete;
@@ -217,6 +270,13 @@ inline RecordStream::RecordStream(const std::string& path, const std::string& ge
 		}
 		if (independent) for (uint32_t i = 0; i < n; ++i) dom_sparse.push_back(rd<uint32_t>(p, e));
 	}
+	if (const int s_qd = ar.id("hipqdomains"); s_qd >= 0 && fastq)
+	{
+		std::vector<uint8_t> db; uint64_t dm = 0;
+		if (!ar.part(s_qd, 0, db, dm)) throw std::runtime_error("cannot read the `hipqdomains` stream");
+		if (s_dom >= 0) throw std::runtime_error("an archive holds `hipdomains` or `hipqdomains`, not both");
+		qdomains = parse_qdomains(db, ar.n_parts(s_qual));
+	}
 	if (only_domain >= 0 && (!independent || (size_t)only_domain >= dom_part.size() || !ext_hdr)) throw std::runtime_error("a single domain can be read from an archive with independent domains only");
 	if (only_domain >= 0) read_index = dom_read[only_domain];
 	if (fastq && ar.n_parts(s_qual) != ar.n_parts(s_dna)) throw std::runtime_error("`dna` and `qual` streams have different numbers of parts");
@@ -226,6 +286,13 @@ inline void RecordStream::start()
 {
 	started = true;
 	const size_t n_parts = part_end(), p_first = part_begin();
+	if (qual_batches)
+	{	// The hand-over to the quality thread is bounded by BASES instead of parts: while a batch is decoded the DNA thread gets at most
+		// qual_batch_bases ahead, then waits.  q_reads and q_quals hold what the consumer cannot take before the batch's qualities
+		// arrive — the batch in work and the one being collected — and nothing else reaches them, so they need no count of their own.
+		q_bases_for_qual.cap = q_reads.cap = q_quals.cap = ~(size_t)0;
+		q_bases_for_qual.weight_cap = qual_batch_bases;
+	}
 	t_dna = std::thread([this, n_parts, p_first]() {
 		cl_dna_decoder* d = nullptr;
 		try {
@@ -257,7 +324,7 @@ inline void RecordStream::start()
 			if (s != CL_OK) { err_dna = cl_dna_decoder_error(d); break; }
 			x.bases.resize(got);
 			if (want_digest) { if (!dg_bases_host(x.bases.data(), x.off.data(), n_reads, g, &dig_dna)) { err_dna = "more reads than the content digest can index"; break; } g += n_reads; }
-			if (fastq) { ReadPart cp; cp.bases = x.bases; cp.off = x.off; q_bases_for_qual.push(std::move(cp)); }
+			if (fastq) { ReadPart cp; cp.bases = x.bases; cp.off = x.off; const uint64_t w = cp.bases.size(); q_bases_for_qual.push(std::move(cp), w); }
 			q_reads.push(std::move(x));
 		}
 		} catch (const std::exception& e) { err_dna = std::string("corrupt `dna` part (") + e.what() + ")"; }
@@ -274,10 +341,46 @@ inline void RecordStream::start()
 		if (q && want_digest && cl_qual_decoder_set_digest(q, 1, first_read_index()) != CL_OK) { err_qual = "cl_qual_decoder_set_digest"; cl_qual_decoder_free(q); q = nullptr; }
 		ReadPart x; std::vector<uint8_t> in; uint64_t meta = 0; size_t p = part_begin(); const size_t p_first = p;
 		try {
+		if (q && qual_batches)
+		{	// whole model domains, many at a time (set_qual_batch_decoder)
+			QualBatch B; uint64_t g = first_read_index();
+			auto flush = [&]() {
+				if (B.parts.empty()) return;
+				qual_batches(qpar, B, want_digest && M.qual_mode != 8 ? &dig_qual : nullptr);
+				for (ReadPart& y : B.parts)
+				{
+					if (y.quals.size() != y.bases.size()) throw std::runtime_error("the batch decoder left a part without its qualities");
+					y.bases.clear(); y.bases.shrink_to_fit();
+					q_quals.push(std::move(y));
+				}
+				B = QualBatch(); B.first_read = g;
+			};
+			while (q_bases_for_qual.pop(x))
+			{
+				if (!ar.part(s_qual, p, in, meta)) { err_qual = "cannot read a `qual` part"; break; }
+				const uint64_t nr = x.off.size() - 1;
+				if (is_qdomain_start(p))
+				{
+					check_qdomain_read(p, g);
+					// a batch ends where a domain ends: full by its bases, or as many reads and parts as the decoder's 32-bit counts take
+					if (B.n_bases >= qual_batch_bases || B.n_reads + nr > (1ull << 31) || B.parts.size() > (1ull << 30)) flush();
+					B.domain_first.push_back((uint32_t)B.parts.size());
+				}
+				else if (B.parts.empty()) { err_qual = "a `qual` part before the first model domain"; break; }
+				B.n_reads += nr; B.n_bases += x.bases.size(); g += nr;
+				B.parts.push_back(std::move(x)); B.payloads.push_back(std::move(in));
+				++p;
+			}
+			if (err_qual.empty()) flush();
+			cl_qual_decoder_free(q); q = nullptr;                               // (the host decoder was not needed; its digest stays untouched)
+		}
+		uint64_t reads_before = first_read_index();
 		while (q && q_bases_for_qual.pop(x))
 		{
 			if (!ar.part(s_qual, p, in, meta)) { err_qual = "cannot read a `qual` part"; break; }
-			if (p > p_first && is_domain_start(p)) cl_qual_decoder_new_domain(q);
+			if (is_qdomain_start(p)) check_qdomain_read(p, reads_before);
+			reads_before += x.off.size() - 1;
+			if (p > p_first && (is_domain_start(p) || is_qdomain_start(p))) cl_qual_decoder_new_domain(q);
 			x.quals.resize(x.bases.size());
 			if (cl_qual_decode_part(q, in.data(), in.size(), x.bases.data(), x.off.data(), (uint32_t)(x.off.size() - 1), x.quals.data()) != CL_OK) { err_qual = "corrupt `qual` part"; break; }
 			x.bases.clear(); x.bases.shrink_to_fit();
@@ -285,8 +388,11 @@ inline void RecordStream::start()
 			++p;
 		}
 		} catch (const std::exception& e) { err_qual = std::string("corrupt `qual` part (") + e.what() + ")"; }
+		// after an error the consumer is told first: it waits for this part's qualities and takes no more reads until then, so the DNA
+		// thread, whose queue of reads is bounded, would never reach the end of what is drained here
+		if (!err_qual.empty()) q_quals.finish();
 		while (q_bases_for_qual.pop(x)) {}                                    // drain after an error so that the producer can finish
-		if (q && want_digest) (void)cl_qual_decoder_digest(q, &dig_qual);
+		if (q && want_digest && !qual_batches) (void)cl_qual_decoder_digest(q, &dig_qual);
 		if (q) cl_qual_decoder_free(q);
 		thread_report("qual");
 		q_quals.finish();

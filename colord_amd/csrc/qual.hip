@@ -14,6 +14,7 @@
 // per part (entr_qual.h:68-79), so one lane codes one part and all parts of a batch run concurrently.
 #include "common.hpp"
 #include <functional>
+#include <atomic>
 #include <deque>
 #include <thread>
 #include <chrono>
@@ -21,41 +22,8 @@
 #include "rc_dev.hpp"
 #include "rc_check.hpp"    // the opt-in check of the coded parts (cl_ctx_set_verify_streams)
 #include "digest.hpp"      // qual_bin_map
+#include "qual_ctx.hpp"    // QualCfg and the context of a position, shared with the device decoder (qual_decode.hip)
 #include <algorithm>
-
-namespace {
-
-enum { QM_ORIGINAL = 0, QM_QUINARY_AVG, QM_QUAD_AVG, QM_BINARY_AVG, QM_QUINARY_THR, QM_QUAD_THR, QM_BINARY_THR, QM_AVERAGE, QM_NONE };
-
-struct QualCfg {
-	int32_t mode, level;
-	uint32_t bits_per_sym, n_ctx_sym, ctx_bits;   // previous-symbol history
-	uint32_t base_bits;                            // neighbouring-base part of the context
-	uint32_t n_sym, sym_bits;                      // alphabet of the per-base family
-	uint32_t n_bins, navg;                         // *-avg: bins and coded bytes per read (2 per bin; avg: 2)
-	uint32_t max_total, adder;
-	uint32_t n_ctx;                                // dense context count of the per-base family
-	uint32_t is_avg, is_thr;
-	uint32_t hist_radix, n_hist;                   // values a history field takes, and histories: hist_radix ^ n_ctx_sym (qual_hist_radix)
-	uint32_t dense_bits;                           // bits of a context id: ids are 0 .. n_ctx - 1 <= 2^dense_bits
-	uint8_t map_fwd[96], quant[96];
-};
-
-// ---- context ids ------------------------------------------------------------------------------------
-// The id of a context is private to this file: the sort only has to bring equal contexts together in stream order, and the models start
-// uniform (k_init_state), so any one-to-one numbering gives the same triples.  Ids are therefore DENSE: a history field holds a symbol
-// 0 .. n_sym - 1 or "no such position" (= n_sym), the n_ctx_sym fields are packed in base n_sym + 1, and the base context (and the
-// edit-script flags of levels 2 and 3) multiply on top.  4-avg / 4-thr: 125 histories x 256 = 32 000 ids, 15 bits (bit fields: 17);
-// 5-*: 216 x 256, 16 bits (17); 2-*: 729 x 256, 18 bits (20).  QM_ORIGINAL keeps its bit fields: the quantised values fill them.
-__host__ __device__ inline uint32_t qual_hist_radix(const QualCfg& c) { return c.mode == QM_ORIGINAL ? 1u << c.bits_per_sym : c.n_sym + 1; }
-// history so far + the field of the position t + 1 back, whose place value is `place` (1, radix, radix^2 ...)
-__host__ __device__ inline uint32_t qual_hist_add(uint32_t hist, uint32_t place, uint32_t field) { return hist + place * field; }
-__host__ __device__ inline uint32_t qual_ctx_id(const QualCfg& c, uint32_t hist, uint32_t bctx, uint32_t fl)
-{
-	return hist + c.n_hist * (bctx | (fl << c.base_bits));
-}
-
-} // namespace
 
 // The model-independent half of cl_qual_encode for a batch of parts: per group of parts the interleaved triple layout, the
 // (context, symbol) key and triple slot of every coded symbol, the stable sort by context and the context runs.  It depends on the
@@ -63,12 +31,14 @@ __host__ __device__ inline uint32_t qual_ctx_id(const QualCfg& c, uint32_t hist,
 // evolution and interval coding of the batch before (cl_qual_prepare_batch).
 struct QualGroupPrep {
 	uint32_t p0 = 0, p1 = 0, np = 0, ng = 0; uint64_t n_base = 0, n_syms = 0, n_byte = 0, trip_words = 0;
+	bool domain_start = false;                         // the models start afresh before this group's evolution
 	std::vector<uint32_t> rank, plen_r;
 	DevBuf<uint64_t> d_gbase; DevBuf<uint32_t> d_plen;
 	DevBuf<uint32_t> key, sidx, bkey, bsidx, bss, bse;
 };
 struct QualPrepared {
 	const cl_reads* R = nullptr; const uint8_t* d_quals = nullptr; std::vector<uint32_t> part_bounds;
+	uint64_t dom_n = 0, since_in = 0, since_out = 0;   // model domains (cl_qual_coder_set_domain_symbols): the setting and the symbols of the open domain the cuts were made from / leave behind
 	std::vector<std::unique_ptr<QualGroupPrep>> groups;
 };
 struct cl_qual_coder {
@@ -79,6 +49,12 @@ struct cl_qual_coder {
 	DevBuf<uint32_t> state;       // per-base family: n_ctx * (n_sym + 1)  (counters..., total)
 	DevBuf<uint32_t> bstate;      // byte family: 896 * 257
 	uint64_t symbols_coded = 0;
+	// model domains: dom_n symbols (0: none) close a domain at the next part boundary.  dom_since / parts_evolved / dom_first follow the
+	// model evolution (the one place the batches pass in order); prep_since is the preparation worker's own count, one batch after the
+	// other — a prepared batch whose count differs from the evolution's is made again (qual_evolve_batch)
+	uint64_t dom_n = 0, dom_since = 0, parts_evolved = 0;
+	std::vector<uint64_t> dom_first{ 0 };
+	std::atomic<uint64_t> prep_since{ 0 };
 	std::unique_ptr<QualPrepared> ahead;   // the next batch, prepared ahead
 	std::deque<std::unique_ptr<struct QualEvolved>> evolved;   // the next batches, their models evolved and their interval coders running (cl_qual_evolve_ahead)
 	std::function<cl_status()> before_tail;        // called by cl_qual_encode before it waits for the interval coders of its batch
@@ -99,12 +75,7 @@ struct QualEvolved {
 cl_qual_coder::~cl_qual_coder() { evolved.clear(); for (hipStream_t s : cstreams) (void)hipStreamDestroy(s); }
 
 namespace {
-constexpr uint32_t BYTE_CTX = 5 * 128 + 256;      // (bin, floor(prev avg)) and 0x100 + high byte (quality_coder_impl.cpp:821-834)
-
-__device__ inline uint32_t arena_base(const uint64_t* __restrict__ packed, uint64_t wb, uint32_t p)
-{
-	return (uint32_t)(packed[wb + (p >> 5)] >> (62 - 2 * (p & 31))) & 3u;
-}
+constexpr uint32_t BYTE_CTX = QUAL_BYTE_CTX;
 
 // ---- Q1: (context, symbol) of every coded symbol, in stream order ---------------------------------
 // one wave per read.  key32 = ctx << sym_bits | sym ; byte family: bkey = ctx << 8 | byte
@@ -153,8 +124,8 @@ __global__ __launch_bounds__(256) void k_qual_symbols(const QualCfg* __restrict_
 			{
 				double avg = (double)sum[0] / (double)len;            // quality_coder_impl.cpp:438-450 (0/0 -> NaN -> cast 0 on x86: len==0 unsupported)
 				uint32_t a = (uint32_t)(avg * 256), a1 = a >> 8, a2 = a & 0xff;
-				bkey[bo] = (0u << 8) | a1; bsidx[bo] = trip_index(lay, part, s_read);
-				bkey[bo + 1] = ((640u + a1) << 8) | a2; bsidx[bo + 1] = trip_index(lay, part, s_read + 1);
+				bkey[bo] = (qual_avg_ctx_hi(0, 0) << 8) | a1; bsidx[bo] = trip_index(lay, part, s_read);
+				bkey[bo + 1] = (qual_avg_ctx_lo(a1) << 8) | a2; bsidx[bo + 1] = trip_index(lay, part, s_read + 1);
 			}
 			else
 			{
@@ -163,8 +134,8 @@ __global__ __launch_bounds__(256) void k_qual_symbols(const QualCfg* __restrict_
 				{
 					double avg = cnt[t] ? (double)sum[t] / (double)cnt[t] : 0.0;
 					uint32_t a = (uint32_t)(avg * 256), a1 = a >> 8, a2 = a & 0xff;
-					bkey[bo + 2 * t] = ((t * 128u + ctx_p) << 8) | a1; bsidx[bo + 2 * t] = trip_index(lay, part, s_read + 2 * t);
-					bkey[bo + 2 * t + 1] = ((640u + a1) << 8) | a2; bsidx[bo + 2 * t + 1] = trip_index(lay, part, s_read + 2 * t + 1);
+					bkey[bo + 2 * t] = (qual_avg_ctx_hi(t, ctx_p) << 8) | a1; bsidx[bo + 2 * t] = trip_index(lay, part, s_read + 2 * t);
+					bkey[bo + 2 * t + 1] = (qual_avg_ctx_lo(a1) << 8) | a2; bsidx[bo + 2 * t + 1] = trip_index(lay, part, s_read + 2 * t + 1);
 					ctx_p = (uint32_t)avg;
 				}
 			}
@@ -172,36 +143,19 @@ __global__ __launch_bounds__(256) void k_qual_symbols(const QualCfg* __restrict_
 	}
 	if (cfg.mode == QM_AVERAGE || cfg.mode == QM_NONE) { if (__ballot(out_of_range) && lane == 0) atomicOr(bad, 1u); return; }
 
-	const uint32_t radix = cfg.hist_radix, missing = radix - 1;
 	for (uint32_t i = lane; i < len; i += 64)
 	{
 		uint32_t qv = quals[qb + i] - 33u;
 		if (qv > 95u) { out_of_range = true; qv = 0; }
 		uint32_t sym = cfg.map_fwd[qv];
-		// history: context values of positions i-1 .. i-n (missing = the field's last value), packed in base `radix`
-		uint32_t hist = 0, place = 1;
-		for (uint32_t t = 1; t <= cfg.n_ctx_sym; ++t, place *= radix)
-		{
-			uint32_t v = missing;
-			if (i >= t)
-			{
-				const uint32_t qp = quals[qb + i - t] - 33u;                          // (checked at its own position)
-				uint32_t s = cfg.map_fwd[qp > 95u ? 0u : qp];
-				v = cfg.mode == QM_ORIGINAL ? (cfg.quant[s] & missing) : s;
-			}
-			hist = qual_hist_add(hist, place, v);
-		}
-		uint32_t b0 = arena_base(packed, wb, i);
-		uint32_t bm1 = i > 0 ? arena_base(packed, wb, i - 1) : 0;
-		uint32_t bm2 = i > 1 ? arena_base(packed, wb, i - 2) : 0;
-		uint32_t bp1 = i + 1 < len ? arena_base(packed, wb, i + 1) : 0;
-		uint32_t bctx;
-		if (cfg.is_avg) bctx = (bm2 << 6) | (bm1 << 4) | (b0 << 2) | bp1;                       // :203-210
-		else if (cfg.is_thr) bctx = b0 | (bm1 << 2) | (bm2 << 4) | (bp1 << 6);                  // :323-339
-		else if (cfg.level == 3) bctx = b0 | (bm1 << 2) | (bm2 << 4) | (bp1 << 6);              // :88-108
-		else bctx = b0 | (bm1 << 2) | ((uint32_t)(i > 1 && bm2 == bm1) << 4) | (bp1 << 5);
+		// history: context values of positions i-1 .. i-n
+		const uint32_t hist = qual_hist_of(cfg, i, [&](uint32_t t) {
+			const uint32_t qp = quals[qb + i - t] - 33u;                              // (checked at its own position)
+			return qual_hist_field(cfg, cfg.map_fwd[qp > 95u ? 0u : qp]);
+		});
+		const uint32_t bctx = qual_base_ctx_at(cfg, packed, wb, i, len);
 		uint32_t fl = 0;
-		if (cfg.level > 1 && flags) { uint8_t c = flags[qb + i]; fl = (c == 'M' ? 1u : 0u) | (c == 'A' ? 2u : 0u); }
+		if (cfg.level > 1 && flags) fl = qual_flag_bits(flags[qb + i]);
 		key[k_read + i] = (qual_ctx_id(cfg, hist, bctx, fl) << cfg.sym_bits) | sym;
 		sidx_out[k_read + i] = trip_index(lay, part, s_read + navg + i);
 	}
@@ -411,15 +365,11 @@ void fill_range(uint8_t* a, int lo, int hi, uint8_t v) { for (int i = lo; i < hi
 } // namespace
 
 // CQualityCoder::Init (quality_coder.cpp:26-247): mode tables; adjust_quality_map_* (:250-525)
-extern "C" cl_status cl_qual_coder_create(cl_ctx* ctx, const cl_qual_params* prm, cl_qual_coder** out)
+cl_status qual_make_cfg(cl_ctx* ctx, const cl_qual_params* prm, QualCfg& c)
 {
-	if (!ctx || !prm || !out) return cl_fail(ctx, CL_E_INVALID, "cl_qual_coder_create: null argument");
 	if (prm->mode < 0 || prm->mode > QM_NONE || prm->source < 0 || prm->source > 2 || prm->level < 1 || prm->level > 3)
 		return cl_fail(ctx, CL_E_INVALID, "cl_qual_coder_create: mode 0..8, source 0..2, level 1..3");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	cl_qual_coder* Q = new cl_qual_coder(); Q->ctx = ctx; Q->prm = *prm;
-	std::unique_ptr<cl_qual_coder> guard(Q);
-	QualCfg& c = Q->cfg; memset(&c, 0, sizeof(c));
+	memset(&c, 0, sizeof(c));
 	c.mode = prm->mode; c.level = prm->level;
 	c.max_total = 1u << 18; c.adder = 8;                                    // quality_coder.h:37-41
 	auto bins = [&](uint32_t n) -> cl_status {
@@ -468,13 +418,30 @@ extern "C" cl_status cl_qual_coder_create(cl_ctx* ctx, const cl_qual_params* prm
 	c.dense_bits = 0; while ((1ull << c.dense_bits) < c.n_ctx) ++c.dense_bits;
 	if (c.dense_bits + c.sym_bits > 32 || (c.n_ctx > 1 && qual_ctx_id(c, c.n_hist - 1, (1u << c.base_bits) - 1, c.level > 1 ? 3u : 0u) != c.n_ctx - 1))
 		return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_qual_coder_create: context ids do not fit the bits the sort is asked for");
+	return CL_OK;
+}
+// the initial state of n_ctx models of n_sym symbols, on the context's launch stream (a coder's creation, the start of a model domain, the
+// device decoder's tables)
+cl_status qual_init_state(cl_ctx* ctx, uint32_t* d_state, uint64_t n_ctx, uint32_t n_sym)
+{
+	LAUNCH(ctx, k_init_state, grid_for(n_ctx * (n_sym + 1), 256), 256, d_state, n_ctx, n_sym);
+	HIP_TRY(ctx, hipGetLastError());
+	return CL_OK;
+}
+extern "C" cl_status cl_qual_coder_create(cl_ctx* ctx, const cl_qual_params* prm, cl_qual_coder** out)
+{
+	if (!ctx || !prm || !out) return cl_fail(ctx, CL_E_INVALID, "cl_qual_coder_create: null argument");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	cl_qual_coder* Q = new cl_qual_coder(); Q->ctx = ctx; Q->prm = *prm;
+	std::unique_ptr<cl_qual_coder> guard(Q);
+	QualCfg& c = Q->cfg;
+	CL_TRY(qual_make_cfg(ctx, prm, c));
 	DEV_ALLOC(ctx, Q->d_cfg, 1);
 	HIP_TRY(ctx, hipMemcpyAsync(Q->d_cfg.p, &c, sizeof(c), hipMemcpyHostToDevice, ctx->stream));
 	DEV_ALLOC(ctx, Q->state, (uint64_t)c.n_ctx * (c.n_sym + 1));
-	LAUNCH(ctx, k_init_state, grid_for((uint64_t)c.n_ctx * (c.n_sym + 1), 256), 256, Q->state.p, (uint64_t)c.n_ctx, c.n_sym);
+	CL_TRY(qual_init_state(ctx, Q->state.p, c.n_ctx, c.n_sym));
 	DEV_ALLOC(ctx, Q->bstate, (uint64_t)BYTE_CTX * 257);
-	LAUNCH(ctx, k_init_state, grid_for((uint64_t)BYTE_CTX * 257, 256), 256, Q->bstate.p, (uint64_t)BYTE_CTX, 256u);
-	HIP_TRY(ctx, hipGetLastError());
+	CL_TRY(qual_init_state(ctx, Q->bstate.p, BYTE_CTX, 256u));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	*out = guard.release();
 	return CL_OK;
@@ -483,10 +450,31 @@ extern "C" cl_ctx* cl_qual_coder_ctx(const cl_qual_coder* q) { return q ? q->ctx
 const cl_qual_params* cl_qual_coder_params(const cl_qual_coder* q) { return q ? &q->prm : nullptr; }
 extern "C" void cl_qual_coder_free(cl_qual_coder* q) { delete q; }
 
+// ---- model domains -------------------------------------------------------------------------------------------------------------
+// The reference keeps one adaptive model set for the whole file (entr_qual.h:100-135), which makes its decoder one dependent chain
+// (entr_qual.h:136-260).  With n > 0 the models start afresh — exactly as a new coder's — at the first part boundary at which the open
+// domain holds n coded symbols or more, so that a decoder can run the domains side by side (cl_qual_decode_domains).
+extern "C" cl_status cl_qual_coder_set_domain_symbols(cl_qual_coder* q, uint64_t n)
+{
+	if (!q) return CL_E_INVALID;
+	if (q->ahead || !q->evolved.empty()) return cl_fail(q->ctx, CL_E_INVALID, "cl_qual_coder_set_domain_symbols: a batch is prepared or evolved ahead");
+	q->dom_n = n;
+	q->prep_since = q->dom_since;
+	return CL_OK;
+}
+extern "C" cl_status cl_qual_coder_domains(const cl_qual_coder* q, uint64_t* h_first_part, uint64_t cap, uint64_t* n_out)
+{
+	if (!q || !n_out || (cap && !h_first_part)) return CL_E_INVALID;
+	*n_out = q->dom_first.size();
+	if (q->dom_first.size() > cap) return cl_fail(q->ctx, CL_E_CAPACITY, "cl_qual_coder_domains: capacity");
+	std::copy(q->dom_first.begin(), q->dom_first.end(), h_first_part);
+	return CL_OK;
+}
+
 // CEntrComprQuals::Compress for a batch of whole parts (entr_qual.h:100-135).  Models persist across calls.
 namespace {
 cl_status qual_prepare(cl_ctx* ctx, cl_qual_coder* Q, const cl_reads* R, const uint8_t* d_quals, const uint64_t* d_qual_off,
-                       const uint8_t* d_flags, const uint32_t* h_part_bounds, uint32_t n_parts, QualPrepared& P)
+                       const uint8_t* d_flags, const uint32_t* h_part_bounds, uint32_t n_parts, uint64_t since_in, QualPrepared& P)
 {
 	const QualCfg& c = Q->cfg;
 	P.R = R; P.d_quals = d_quals; P.part_bounds.assign(h_part_bounds, h_part_bounds + n_parts + 1);
@@ -517,14 +505,25 @@ cl_status qual_prepare(cl_ctx* ctx, cl_qual_coder* Q, const cl_reads* R, const u
 	// duration is set by the longest part, not by the number of parts), so groups are made as large as 32-bit
 	// symbol indices allow: every extra launch would pay that latency again.
 	const uint64_t GROUP_SYMS = (1ull << 31) - (1ull << 24);
+	const bool per_base = !(c.mode == QM_AVERAGE);
+	auto syms_of = [&](uint32_t a, uint32_t b) { return (per_base ? (qo[b] - qo[a]) : 0) + (uint64_t)(h_part_bounds[b] - h_part_bounds[a]) * c.navg; };
+	// model domains: a part opens a new one when the open domain has reached dom_n symbols.  A group never spans a domain start: the
+	// models' evolution is per group, and the reset goes between two of them (qual_evolve_batch)
+	std::vector<uint8_t> opens(n_parts, 0);
+	P.dom_n = Q->dom_n; P.since_in = since_in;
+	for (uint32_t p = 0; p < n_parts; ++p)
+	{
+		if (P.dom_n && since_in >= P.dom_n) { opens[p] = 1; since_in = 0; }
+		since_in += syms_of(p, p + 1);
+	}
+	P.since_out = since_in;
 	uint32_t p0 = 0;
 	while (p0 < n_parts)
 	{
 		auto Gp = std::make_unique<QualGroupPrep>(); QualGroupPrep& G = *Gp;
 		uint32_t p1 = p0 + 1;
-		const bool per_base = !(c.mode == QM_AVERAGE);
-		auto syms_of = [&](uint32_t a, uint32_t b) { return (per_base ? (qo[b] - qo[a]) : 0) + (uint64_t)(h_part_bounds[b] - h_part_bounds[a]) * c.navg; };
-		while (p1 < n_parts && syms_of(p0, p1 + 1) <= GROUP_SYMS) ++p1;
+		while (p1 < n_parts && !opens[p1] && syms_of(p0, p1 + 1) <= GROUP_SYMS) ++p1;
+		G.domain_start = opens[p0] != 0;
 		const uint32_t r0 = h_part_bounds[p0], r1 = h_part_bounds[p1];
 		const uint64_t n_base = qo[p1] - qo[p0], n_syms = syms_of(p0, p1), n_byte = (uint64_t)(r1 - r0) * c.navg;
 		if (n_syms >= (1ull << 32)) return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_qual_encode: a single part has >= 2^32 symbols");
@@ -596,7 +595,8 @@ cl_status cl_qual_prepare_batch(cl_ctx* ctx, cl_qual_coder* Q, const cl_reads* R
 	for (uint32_t p = 0; p < n_parts; ++p) if (h_part_bounds[p] > h_part_bounds[p + 1]) return CL_E_INVALID;
 	if (h_part_bounds[n_parts] > R->n_reads) return CL_E_INVALID;
 	auto P = std::make_unique<QualPrepared>();
-	CL_TRY(qual_prepare(ctx, Q, R, d_quals, d_qual_off, d_flags, h_part_bounds, n_parts, *P));
+	CL_TRY(qual_prepare(ctx, Q, R, d_quals, d_qual_off, d_flags, h_part_bounds, n_parts, Q->prep_since.load(), *P));
+	Q->prep_since = P->since_out;                                              // (the batches are prepared in the order they are coded in; if not, the evolution makes this one again)
 	*out = P.release();
 	return CL_OK;
 }
@@ -611,7 +611,9 @@ cl_status qual_evolve_batch(cl_ctx* ctx, cl_qual_coder* Q, const cl_reads* R, co
 	const QualCfg& c = Q->cfg;
 	// the model-independent half: made ahead (cl_qual_prepare_batch) for exactly this batch, or here
 	if (Pp && !(Pp->R == R && Pp->d_quals == d_quals && Pp->part_bounds.size() == (size_t)n_parts + 1 && memcmp(Pp->part_bounds.data(), h_part_bounds, ((size_t)n_parts + 1) * 4) == 0)) Pp.reset();
-	if (!Pp) { Pp = std::make_unique<QualPrepared>(); CL_TRY(qual_prepare(ctx, Q, R, d_quals, d_qual_off, d_flags, h_part_bounds, n_parts, *Pp)); }
+	// (its groups must be cut at the domain starts that follow from the symbols evolved so far: never models carried across one)
+	if (Pp && !(Pp->dom_n == Q->dom_n && (Q->dom_n == 0 || Pp->since_in == Q->dom_since))) Pp.reset();
+	if (!Pp) { Pp = std::make_unique<QualPrepared>(); CL_TRY(qual_prepare(ctx, Q, R, d_quals, d_qual_off, d_flags, h_part_bounds, n_parts, Q->dom_since, *Pp)); }
 	E.R = R; E.d_quals = d_quals; E.part_bounds.assign(h_part_bounds, h_part_bounds + n_parts + 1);
 	const uint32_t bits_max = c.max_total == (1u << 20) ? 20 : 18;
 	const uint64_t* inv_tab = nullptr;
@@ -621,6 +623,12 @@ cl_status qual_evolve_batch(cl_ctx* ctx, cl_qual_coder* Q, const cl_reads* R, co
 		QualGroupPrep& G = *Gp;
 		const uint32_t np = G.np, ng = G.ng;
 		const uint64_t n_base = G.n_base, n_syms = G.n_syms, n_byte = G.n_byte;
+		if (G.domain_start)
+		{	// a new model domain: both families as a fresh coder has them, on this stream behind the evolution of the group before
+			CL_TRY(qual_init_state(ctx, Q->state.p, c.n_ctx, c.n_sym));
+			CL_TRY(qual_init_state(ctx, Q->bstate.p, BYTE_CTX, 256u));
+			Q->dom_first.push_back(Q->parts_evolved + G.p0);
+		}
 		auto Pn = std::make_unique<QualPending>(); QualPending& PG = *Pn;
 		PG.p0 = G.p0; PG.np = np; PG.rank = G.rank; PG.n_syms = n_syms;
 		PG.d_gbase = std::move(G.d_gbase); PG.d_plen = std::move(G.d_plen);
@@ -668,6 +676,7 @@ cl_status qual_evolve_batch(cl_ctx* ctx, cl_qual_coder* Q, const cl_reads* R, co
 		}
 		E.groups.push_back(std::move(Pn));
 	}
+	Q->dom_since = Pp->since_out; Q->parts_evolved += n_parts;
 	return CL_OK;
 }
 } // namespace
@@ -704,6 +713,7 @@ extern "C" cl_status cl_qual_encode(cl_ctx* ctx, cl_qual_coder* Q, const cl_read
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 		for (uint32_t p = 0; p < n_parts; ++p) h_part_sizes[p] = 8;
 		*n_out = 8ull * n_parts;
+		Q->parts_evolved += n_parts;                                             // (no symbols: a domain never fills)
 		return CL_OK;
 	}
 	if (Ep)

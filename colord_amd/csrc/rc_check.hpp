@@ -29,6 +29,16 @@ RC_HD inline uint64_t rc_mulhi64(uint64_t a, uint64_t b)
 #endif
 }
 
+// range / tot as in k_range_code, inv = floor((2^64-1) / tot): the high product is the quotient or one below it, the remainder it
+// leaves is below 2 tot < 2^22.  (The decoder's `range /= tot` of GetCumulativeFreq, sub_rc.h:264-268; a decoder that has to FIND its
+// symbol — k_qual_decode — compares q t <= buffer for the cumulative counts t before it takes the step below.)
+RC_HD inline uint64_t rc_quotient(uint64_t range, uint32_t tot, uint64_t inv)
+{
+	uint64_t q = rc_mulhi64(range, inv);
+	const uint32_t rem = (uint32_t)range - (uint32_t)q * tot;
+	return q + (uint32_t)(rem >= tot);
+}
+
 // One symbol of the decoder (sub_rc.h:264-286) whose interval is known: t = cum << 42 | freq << 21 | tot, inv = floor((2^64-1) / tot).
 // false: the symbol does not decode — a triple that is no interval (tot == 0, freq == 0, cum + freq > tot; nothing is computed from it),
 // or a buffer outside the symbol's interval: with q = range / tot, cum <= buffer / q < cum + freq  <=>  q cum <= buffer < q (cum + freq)
@@ -42,10 +52,7 @@ RC_HD inline bool rc_check_step(uint64_t& low, uint64_t& range, uint64_t& buffer
 {
 	const uint32_t tot = (uint32_t)(t & 0x1fffff), freq = (uint32_t)((t >> 21) & 0x1fffff), cum = (uint32_t)(t >> 42);
 	if (tot == 0 || freq == 0 || cum + freq > tot) return false;
-	// range / tot as in k_range_code: the high product is the quotient or one below it, the remainder it leaves is below 2 tot < 2^22
-	uint64_t q = rc_mulhi64(range, inv);
-	const uint32_t rem = (uint32_t)range - (uint32_t)q * tot;
-	q += (uint32_t)(rem >= tot);
+	const uint64_t q = rc_quotient(range, tot, inv);
 	const uint64_t r = q * cum;
 	if (buffer < r || buffer - r >= q * freq) return false;
 	buffer -= r; low += r; range = q * freq;

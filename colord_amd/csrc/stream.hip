@@ -341,6 +341,7 @@ extern "C" cl_status cl_compressor_refs_finish(cl_compressor* c)
 		cl_ctx* qc = (c->P.level <= 1) ? c->qctx : ctx;        // levels 2 and 3 need the edit scripts: same stream as the DNA path
 		const cl_status s = cl_qual_coder_create(qc, &c->Q, &c->qual);
 		if (s != CL_OK) return cl_fail(ctx, s, std::string("quality coder: ") + cl_last_error(qc));
+		CL_TRY(cl_qual_coder_set_domain_symbols(c->qual, c->qual_domain_symbols));
 	}
 	c->phase = 2;
 	return CL_OK;
@@ -393,6 +394,27 @@ extern "C" cl_status cl_compressor_encode(cl_compressor* c, const cl_reads* read
 	}
 	info->n_anchors = job->n_anchors; info->tuple_bytes = job->es_bytes;
 	return coder.code(c->refs, *job);
+}
+
+// model domains of the quality stream (cl_qual_coder_set_domain_symbols): before anything of pass 2b has seen the coder
+extern "C" cl_status cl_compressor_set_qual_domain_symbols(cl_compressor* c, uint64_t n)
+{
+	if (!c) return CL_E_INVALID;
+	if (!c->has_qual) return cl_fail(c->ctx, CL_E_INVALID, "cl_compressor_set_qual_domain_symbols: no quality stream");
+	{
+		std::lock_guard<std::mutex> l(c->la.lane_mu);
+		if (c->enc_chunk || c->la.n_announced) return cl_fail(c->ctx, CL_E_INVALID, "cl_compressor_set_qual_domain_symbols: call before the first cl_compressor_encode / cl_compressor_prepare_parts");
+	}
+	c->qual_domain_symbols = n;
+	if (c->qual) { const cl_status s = cl_qual_coder_set_domain_symbols(c->qual, n); if (s != CL_OK) return cl_fail(c->ctx, s, std::string("quality coder: ") + cl_last_error(cl_qual_coder_ctx(c->qual))); }
+	return CL_OK;
+}
+extern "C" cl_status cl_compressor_qual_domains(const cl_compressor* c, uint64_t* h_first_part, uint64_t cap, uint64_t* n_out)
+{
+	if (!c || !n_out) return CL_E_INVALID;
+	if (!c->qual) return cl_fail(c->ctx, CL_E_INVALID, "cl_compressor_qual_domains: no quality coder (yet)");
+	const cl_status s = cl_qual_coder_domains(c->qual, h_first_part, cap, n_out);
+	return s == CL_OK ? CL_OK : cl_fail(c->ctx, s, "cl_compressor_qual_domains: capacity");
 }
 
 extern "C" cl_status cl_compressor_verified(const cl_compressor* c, uint64_t* reads, uint64_t* bases)

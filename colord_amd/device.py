@@ -52,7 +52,8 @@ class _OrderedLib:
     microseconds; a host that embeds the library orders its own streams."""
     _HOST_ONLY = ("cl_last_error", "cl_ctx_kernel_times", "cl_ctx_last_kernel_ms", "cl_ctx_set_timing", "cl_ref_accept", "cl_ctx_set_verify", "cl_ctx_verified",
                   "cl_compressor_verified", "cl_ctx_set_verify_streams", "cl_ctx_verified_streams", "cl_compressor_verified_streams",
-                  "cl_ctx_set_digest", "cl_ctx_digest", "cl_compressor_digest", "cl_digest_bases_host", "cl_digest_bytes_host", "cl_qual_decoder_set_digest", "cl_qual_decoder_digest")
+                  "cl_ctx_set_digest", "cl_ctx_digest", "cl_compressor_digest", "cl_digest_bases_host", "cl_digest_bytes_host", "cl_qual_decoder_set_digest", "cl_qual_decoder_digest",
+                  "cl_qual_coder_domains", "cl_compressor_qual_domains")
 
     def __init__(self, lib, device):
         self._lib, self._device, self._cache = lib, device, {}
@@ -293,6 +294,42 @@ class Context:
         h = N._P()
         _check(self, self.lib.cl_qual_coder_create(self.h, C.byref(prm), C.byref(h)))
         return QualCoder(self, h)
+
+    def qual_decode_domains(self, mode: int, source: int, level: int, fwd, rev, reads: "Reads", payload: torch.Tensor, part_bounds, part_sizes, domain_first_part,
+                            qual_off: torch.Tensor, flags: torch.Tensor | None = None, max_domains_per_launch: int = 0, want_symbols: bool = False):
+        """cl_qual_decode_domains: the `qual` parts of whole model domains decoded on the device, one lane per domain.  Returns the ASCII
+        qualities (a tensor of qual_off[-1] bytes) and, with want_symbols, (symbols, their n_reads + 1 offsets as a numpy array) for
+        cl_digest_bytes_host(kind 2).  A part that does not decode raises ColordHipError(CL_E_MISMATCH) — with the qualities of the
+        other domains in its `.quals`."""
+        prm = N.QualParams()
+        prm.mode, prm.source, prm.level = mode, source, level
+        prm.n_fwd, prm.n_rev = len(fwd), len(rev)
+        for i, v in enumerate(fwd):
+            prm.fwd[i] = v
+        for i, v in enumerate(rev):
+            prm.rev[i] = v
+        pb = np.ascontiguousarray(part_bounds, dtype=np.uint32)
+        ps = np.ascontiguousarray(part_sizes, dtype=np.uint64)
+        dom = np.ascontiguousarray(domain_first_part, dtype=np.uint32)
+        qual_off, payload = qual_off.contiguous(), payload.contiguous()
+        h_off = qual_off.cpu().numpy().astype(np.int64)
+        n_reads = len(h_off) - 1
+        navg = {1: 10, 2: 8, 3: 4, 7: 2}.get(mode, 0)
+        per_base = mode <= 6
+        sym_off = np.arange(n_reads + 1, dtype=np.int64) * navg + (h_off if per_base else 0)
+        quals = torch.zeros(max(1, int(h_off[-1])), dtype=torch.uint8, device=self.device)
+        syms = torch.zeros(max(1, int(sym_off[-1])), dtype=torch.uint8, device=self.device) if want_symbols else None
+        st = self.lib.cl_qual_decode_domains(self.h, C.byref(prm), reads.h, None if flags is None else flags.data_ptr(), payload.data_ptr() if payload.numel() else None, payload.numel(),
+                                             pb.ctypes.data, ps.ctypes.data, len(pb) - 1, dom.ctypes.data, len(dom), max_domains_per_launch,
+                                             quals.data_ptr(), qual_off.data_ptr(), int(h_off[-1]), None if syms is None else syms.data_ptr(), 0 if syms is None else int(sym_off[-1]))
+        try:
+            _check(self, st)
+        except N.ColordHipError as e:
+            e.quals = quals[:int(h_off[-1])]
+            raise
+        if want_symbols:
+            return quals[:int(h_off[-1])], (syms[:int(sym_off[-1])], sym_off.astype(np.uint64))
+        return quals[:int(h_off[-1])]
 
     # ---- a8 ----
     def anchor_candidates(self, reads: "Reads", refs: "Reads", cand_refs: torch.Tensor, cand_n: torch.Tensor, anchor_len: int,
@@ -582,6 +619,24 @@ class QualCoder(_Obj):
             _check(ctx, st)
             return out[:n.value], [int(x) for x in sizes[:n_parts]]
 
+    def set_domain_symbols(self, n: int):
+        """cl_qual_coder_set_domain_symbols: the models start afresh at the first part boundary at which the open domain holds n symbols (0: never)."""
+        _check(self.ctx, self.ctx.lib.cl_qual_coder_set_domain_symbols(self.h, n))
+
+    def domains(self) -> list:
+        """cl_qual_coder_domains: the first part of every model domain so far, counted over the coder's lifetime."""
+        return _domain_list(self.ctx, self.ctx.lib.cl_qual_coder_domains, self.h)
+
+
+def _domain_list(ctx, fn, h):
+    n = C.c_uint64(0)
+    st = fn(h, None, 0, C.byref(n))
+    if st not in (N.CL_OK, N.CL_E_CAPACITY):
+        _check(ctx, st)
+    out = np.zeros(max(1, n.value), np.uint64)
+    _check(ctx, fn(h, out.ctypes.data, out.size, C.byref(n)))
+    return [int(x) for x in out[:n.value]]
+
 
 class Compressor(_Obj):
     """cl_compressor: pass 1 / reference listing / pass 2 over the chunks of an input (csrc/stream.hip)."""
@@ -629,6 +684,14 @@ class Compressor(_Obj):
         d, q = N.Digest(), N.Digest()
         _check(None, self.ctx.lib.cl_compressor_digest(self.h, C.byref(d), C.byref(q)))
         return d.triple(), q.triple()
+
+    def set_qual_domain_symbols(self, n: int):
+        """cl_compressor_set_qual_domain_symbols: model domains of the quality stream; before the first encode / prepare call."""
+        _check(self.ctx, self.ctx.lib.cl_compressor_set_qual_domain_symbols(self.h, n))
+
+    def qual_domains(self) -> list:
+        """cl_compressor_qual_domains: the first `qual` part of every model domain so far."""
+        return _domain_list(self.ctx, self.ctx.lib.cl_compressor_qual_domains, self.h)
 
     def genome_add(self, sequences: "Reads"):
         _check(self.ctx, self.ctx.lib.cl_compressor_genome_add(self.h, sequences.h))

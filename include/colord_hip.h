@@ -223,6 +223,19 @@ cl_status cl_qual_encode(cl_ctx* ctx, cl_qual_coder* q, const cl_reads* reads, c
                          const uint8_t* d_flags, const uint32_t* h_part_bounds, uint32_t n_parts,
                          uint8_t* d_out, uint64_t cap, uint64_t* h_part_sizes, uint64_t* n_out);
 
+/* Model domains of the quality stream (no counterpart in the reference, whose one model set lives for the whole file, entr_qual.h:100-135,
+ * and whose decoder is therefore one dependent chain, entr_qual.h:136-260).  n = 0 (the default): none — every byte and every launch as
+ * without this call.  While n > 0 the coder starts a new domain at the first part boundary at which the symbols coded since the open
+ * domain's start (per-base symbols and average bytes) have reached n: both model families go back to their initial state, exactly a
+ * fresh coder's, behind the evolution of the last part before.  A domain is a whole number of parts; the first starts with the coder.
+ * The parts of a domain are byte for byte those of a fresh cl_qual_coder given the domain's reads alone.  CL_E_INVALID while a batch is
+ * prepared or evolved ahead (cl_compressor_prepare_parts).  The reference's decompressor cannot read such a stream: it carries its
+ * models on (quality_coder.cpp:605-657); cl_qual_decoder_new_domain / cl_qual_decode_domains read it.
+ * cl_qual_coder_domains: the first part of every domain so far (parts counted over the coder's lifetime; the first entry is 0);
+ * *n_out = their number, CL_E_CAPACITY if it exceeds cap (nothing is written then). */
+cl_status cl_qual_coder_set_domain_symbols(cl_qual_coder* q, uint64_t n);
+cl_status cl_qual_coder_domains(const cl_qual_coder* q, uint64_t* h_first_part, uint64_t cap, uint64_t* n_out);
+
 /* ---- a8: m-mer anchors (encoder.cpp:291-493,617-776,1016-1111,1149-1192,1577-1622) ------------------------ */
 typedef struct cl_anchors cl_anchors;
 /* prepareEncodeCandidates + fixOverlaping* for every read of `reads` (non-HiFi path): for each of its <= c candidate
@@ -464,6 +477,12 @@ cl_status cl_compressor_verified_streams(const cl_compressor* c, uint64_t* parts
  * this rank's first read (cl_compressor_info) + the reads of its chunks before */
 cl_status cl_compressor_digest(const cl_compressor* c, cl_digest* dna, cl_digest* qual);
 
+/* cl_qual_coder_set_domain_symbols / cl_qual_coder_domains of the compressor's quality coder.  The setting must be made before the
+ * first cl_compressor_encode or cl_compressor_prepare_parts call (CL_E_INVALID afterwards, and without a quality stream); the `dna`
+ * coder is not touched.  The domains are valid after cl_compressor_refs_finish. */
+cl_status cl_compressor_set_qual_domain_symbols(cl_compressor* c, uint64_t n);
+cl_status cl_compressor_qual_domains(const cl_compressor* c, uint64_t* h_first_part, uint64_t cap, uint64_t* n_out);
+
 /* ---- a17, the inverse path: CRangeDecoder (sub_rc.h:216-392), CDNACoder::Decode (dna_coder.cpp:234-437), CQualityCoder::Decode
  *      (quality_coder.cpp:605-657, quality_coder_impl.cpp:506-559,800-849), CIDCoder::Decode (id_coder.cpp:396-600); drivers
  *      CEntropyDecomprReads / CEntrDecomprQuals / CEntrDecomprHeaders (entr_read.h:146-191, entr_qual.h:136-260, entr_header.cpp:46-80).
@@ -512,6 +531,28 @@ cl_status cl_qual_decode_part(cl_qual_decoder* q, const uint8_t* h_in, uint64_t 
  * from zero.  Mode none decodes nothing and digests nothing.  cl_qual_decoder_digest: the totals so far. */
 cl_status cl_qual_decoder_set_digest(cl_qual_decoder* q, int on, uint64_t first_read);
 cl_status cl_qual_decoder_digest(const cl_qual_decoder* q, cl_digest* out);
+/* The `qual` parts of whole model domains decoded ON THE DEVICE, one lane per domain (k_qual_decode): CEntrDecomprQuals
+ * (entr_qual.h:136-260) over CQualityCoder::Decode (quality_coder.cpp:605-657, quality_coder_impl.cpp:506-559,800-849) and
+ * CRangeDecoder (sub_rc.h:216-392).  params: as for cl_qual_decoder_create (the -T thresholds may be left out, n_fwd = 0: a decoder
+ * never maps a quality to its bin).  reads: the arena of the decoded bases of the parts' reads (cl_reads_pack; the contexts use
+ * neighbouring bases, N as A); part p holds the reads [h_part_bounds[p], h_part_bounds[p + 1]); d_flags: their classes in the form of
+ * cl_es_flags at the offsets d_qual_off (levels 2 and 3; null at level 1); d_in (n_in bytes): the part payloads back to back,
+ * h_part_sizes[n_parts]; domain d = the parts [h_domain_first_part[d], h_domain_first_part[d + 1]) (the first entry 0, ascending; the
+ * last domain ends with the parts).  Output: ASCII qualities at d_qual_off (n_reads + 1 offsets that hold the arena's read lengths, all
+ * inside quals_cap) — byte for byte what cl_qual_decode_part gives for the same parts with cl_qual_decoder_new_domain at every domain
+ * start — and, with d_symbols (symbols_cap bytes; null: not wanted), the symbols as they leave the models, read r at
+ * r * navg + d_qual_off[r] (avg: r * 2; navg = the average bytes of the mode): its average bytes, then one byte per base, the order
+ * cl_digest_quals defines (digest them with cl_digest_bytes_host, kind 2).  Every domain has model tables of its own in device memory
+ * (n_ctx x (n_sym + 1) + 896 x 257 words: 0.7 MB for 4-avg, 13 MB for org at level 1, 102 MB at level 3): a launch decodes as many
+ * domains as fit COLORD_HIP_QDEC_BUDGET_MB (default 4096) and at most max_domains_per_launch (0: no limit of its own), further
+ * launches take the rest.  A part that does not decode (a symbol outside its model's interval) or does not end at its size:
+ * CL_E_MISMATCH, the text naming the first such domain and its part; that domain stops there, every other domain is decoded
+ * completely.  No input makes the kernel read or write out of range: bytes past a part's size read as 0, a part decodes exactly the
+ * symbols its reads' lengths ask for. */
+cl_status cl_qual_decode_domains(cl_ctx* ctx, const cl_qual_params* params, const cl_reads* reads, const uint8_t* d_flags,
+                                 const uint8_t* d_in, uint64_t n_in, const uint32_t* h_part_bounds, const uint64_t* h_part_sizes, uint32_t n_parts,
+                                 const uint32_t* h_domain_first_part, uint32_t n_domains, uint32_t max_domains_per_launch,
+                                 uint8_t* d_quals, const uint64_t* d_qual_off, uint64_t quals_cap, uint8_t* d_symbols, uint64_t symbols_cap);
 cl_status cl_id_decoder_create(int32_t header_mode, cl_id_decoder** out);
 void cl_id_decoder_free(cl_id_decoder* c);
 /* One `header` part of n ids -> the ids back to back (without '@' / '>'), h_off[n+1], h_plus[n] (1 = the '+' line repeats the id). */
