@@ -80,6 +80,13 @@ _SIG = {
     "cl_ctx_set_digest": (None, [_P, C.c_int]),
     "cl_ctx_digest": (C.c_int32, [_P, C.POINTER(Digest), C.POINTER(Digest)]),
     "cl_compressor_digest": (C.c_int32, [_P, C.POINTER(Digest), C.POINTER(Digest)]),
+    "cl_ctx_set_digest_values": (None, [_P, C.c_int]),
+    "cl_ctx_digest_values": (C.c_int32, [_P, C.POINTER(Digest)]),
+    "cl_compressor_digest_values": (C.c_int32, [_P, C.POINTER(Digest)]),
+    "cl_digest_qual_values": (C.c_int32, [_P, C.POINTER(QualParams), _P, _P, _P, C.c_uint64, C.POINTER(Digest)]),
+    "cl_qual_values": (C.c_int32, [_P, C.POINTER(QualParams), _P, _P, _P, _P, C.c_uint64]),
+    "cl_qual_values_host": (C.c_int32, [C.POINTER(QualParams), _P, _P, C.c_uint64, _P]),
+    "cl_digest_qual_values_host": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(Digest)]),
     "cl_digest_bases": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(Digest)]),
     "cl_digest_quals": (C.c_int32, [_P, C.POINTER(QualParams), _P, _P, _P, C.c_uint64, C.POINTER(Digest)]),
     "cl_digest_bases_host": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(Digest)]),

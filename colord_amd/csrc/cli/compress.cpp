@@ -199,6 +199,8 @@ int run_compress(int argc, char** argv)
 	if (O.verify_scripts) cl_ctx_set_verify(ctx, 1);
 	if (O.verify_streams) cl_ctx_set_verify_streams(ctx, 1);
 	if (O.digest) cl_ctx_set_digest(ctx, 1);
+	const bool digest_values = want_digest_values(O, with_qual);
+	if (digest_values) cl_ctx_set_digest_values(ctx, 1);
 	ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, nullptr, estimated_bases(R), &cmp), "cl_compressor_create");
 	if (O.qual_domain_symbols)
 	{
@@ -317,7 +319,13 @@ int run_compress(int argc, char** argv)
 		cl_digest dd{ 0, 0, 0 }, dq{ 0, 0, 0 };
 		ck(ctx, cl_compressor_digest(cmp, &dd, &dq), "cl_compressor_digest");
 		if (dd.reads != n || dd.symbols != total) die("internal: the content digest did not see every read");
-		add_digest(ar, dd, with_qual && O.P.qual_mode != 8 ? &dq : nullptr, hdr.digest);
+		cl_digest dv{ 0, 0, 0 };
+		if (digest_values)
+		{
+			ck(ctx, cl_compressor_digest_values(cmp, &dv), "cl_compressor_digest_values");
+			if (dv.reads != n || dv.symbols != total) die("internal: the content digest did not see every read");
+		}
+		add_digest(ar, dd, with_qual && O.P.qual_mode != 8 ? &dq : nullptr, hdr.digest, digest_values ? &dv : nullptr);
 	}
 	if (O.qual_domain_symbols)
 	{

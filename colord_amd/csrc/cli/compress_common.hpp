@@ -288,10 +288,24 @@ inline void add_meta(ArchiveWriter& ar, int stream, const Options& O, const Geno
 	                                                    GM.on, GM.stored, GM.read_len, (T.k - 1) * 10, md });
 	ar.add(stream, meta.data(), meta.size(), 0);
 }
-// --digest: the `hipdigest` stream (digest_stream.hpp), before finish_archive; qual: null without a quality stream or in mode none
-inline void add_digest(ArchiveWriter& ar, const cl_digest& dna, const cl_digest* qual, const cl_digest& header)
+// --digest-values: whether this run digests quality values (cl_ctx_set_digest_values).  Without a coded quality stream (-q none, FASTA
+// input) there are none and the run is a plain --digest one: a version-1 stream.
+inline bool want_digest_values(const Options& O, bool with_qual)
 {
-	DigestSet S; S.flags = 1u | (qual ? 2u : 0u) | 4u; S.d[0] = dna; if (qual) S.d[1] = *qual; S.d[2] = header;
+	if (!O.digest_values) return false;
+	if (!with_qual || O.P.qual_mode == 8)
+	{
+		if (O.verbose) fprintf(stderr, "# --digest-values: no coded quality stream (%s): the archive gets the three digests of --digest (`hipdigest` version 1)\n", with_qual ? "-q none" : "the input has no qualities");
+		return false;
+	}
+	for (uint32_t v : O.qd.rev) if (v > 222) die("--digest-values: a -D value above 222 does not fit the quality byte the decoder writes");
+	return true;
+}
+// --digest: the `hipdigest` stream (digest_stream.hpp), before finish_archive; qual: null without a quality stream or in mode none
+// values (--digest-values, and only with qual): the qual-values digest, which makes the stream version 2
+inline void add_digest(ArchiveWriter& ar, const cl_digest& dna, const cl_digest* qual, const cl_digest& header, const cl_digest* values = nullptr)
+{
+	DigestSet S; S.flags = 1u | (qual ? 2u : 0u) | 4u | (qual && values ? 8u : 0u); S.d[0] = dna; if (qual) S.d[1] = *qual; S.d[2] = header; if (qual && values) S.d[3] = *values;
 	const std::vector<uint8_t> b = S.pack();
 	ar.add(ar.reg("hipdigest"), b.data(), b.size(), 0);
 }

@@ -20,7 +20,7 @@ struct RankOut {
 	uint64_t n_reads = 0, mean_read_len = 0; uint32_t sparse_range = 0, n_refs = 0; cl_kmer_stats ks{};
 	uint64_t dna_base = 0, qual_base = 0, qual_framed = 0;     // where its framed `dna` / `qual` parts start in the file; bytes of the latter
 	uint64_t moved = 0;
-	cl_digest dig[2] = { { 0, 0, 0 }, { 0, 0, 0 } }, dig_all[2] = { { 0, 0, 0 }, { 0, 0, 0 } };      // --digest: dna / qual of this rank's reads; of all ranks (as gathered with the byte counts)
+	cl_digest dig[3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } }, dig_all[3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } };      // --digest: dna / qual / (--digest-values) qual-values of this rank's reads; of all ranks (as gathered with the byte counts)
 };
 uint32_t varint_len(uint64_t x) { uint32_t n = 1; for (; x; x >>= 8) ++n; return n; }
 }
@@ -79,6 +79,7 @@ int run_compress_multi(const Options& O)
 		}
 	}
 	HeaderCoder hdr; hdr.want_digest = O.digest; hdr.start(R, (uint32_t)n, O.header_mode);
+	const bool digest_values = want_digest_values(O, with_qual);
 
 	// transports
 	std::vector<std::unique_ptr<Transport>> tp(world);
@@ -114,6 +115,7 @@ int run_compress_multi(const Options& O)
 		// domain's compressor counts from 0, so its chunks are digested here, at their global read indices, when they first reach the device
 		const bool digest_qual = with_qual && O.P.qual_mode != 8;
 		if (O.digest && !independent) cl_ctx_set_digest(ctx, 1);
+		if (digest_values && !independent) cl_ctx_set_digest_values(ctx, 1);
 		ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, T ? &X : nullptr, my_bases, &cmp), "cl_compressor_create");
 		if (GM.on) GM.count_kmers(ctx, cmp);
 		// chunks of whole reader packs (the packs are cut from this rank's first read on: in_reads.cpp:62-77).  The chunk size follows the
@@ -145,6 +147,7 @@ int run_compress_multi(const Options& O)
 			{
 				ck(ctx, cl_digest_bases(ctx, dc.reads, c0, &RO.dig[0]), "content digest");
 				if (digest_qual) ck(ctx, cl_digest_quals(ctx, &prm.qp, dc.reads, dc.d_quals, dc.d_off, c0, &RO.dig[1]), "content digest");
+				if (digest_values) ck(ctx, cl_digest_qual_values(ctx, &prm.qp, dc.reads, dc.d_quals, dc.d_off, c0, &RO.dig[2]), "content digest");
 			}
 			ck(ctx, cl_compressor_count_add(cmp, dc.reads), "pass 1");
 			if (O.stream_input) up.release(dc);                                 // (--stream-input: a chunk leaves HBM after each pass, as in the single-GPU path)
@@ -197,16 +200,19 @@ int run_compress_multi(const Options& O)
 		up.clear();
 		// where this rank's parts go: an all-gather of the framed byte counts, an exclusive sum, pwrite — `dna` of all ranks first, then `qual`
 		if (O.digest && !independent) ck(ctx, cl_compressor_digest(cmp, &RO.dig[0], &RO.dig[1]), "cl_compressor_digest");
-		uint64_t mine[8] = { 0, 0, RO.dig[0].reads, RO.dig[0].symbols, RO.dig[0].sum, RO.dig[1].reads, RO.dig[1].symbols, RO.dig[1].sum };      // framed bytes of `dna`, `qual`; the content digests travel with them
+		if (digest_values && !independent) ck(ctx, cl_compressor_digest_values(cmp, &RO.dig[2]), "cl_compressor_digest_values");
+		// framed bytes of `dna`, `qual`; the content digests travel with them (--digest-values: the fourth triple too, 11 values instead of 8)
+		uint64_t mine[11] = { 0, 0, RO.dig[0].reads, RO.dig[0].symbols, RO.dig[0].sum, RO.dig[1].reads, RO.dig[1].symbols, RO.dig[1].sum, RO.dig[2].reads, RO.dig[2].symbols, RO.dig[2].sum };
+		const uint32_t n_mine = digest_values ? 11 : 8; const int n_dig = digest_values ? 3 : 2;
 		for (size_t p = 0; p < RO.dsz.size(); ++p) mine[0] += varint_len(RO.counts[p]) + RO.dsz[p];
 		for (size_t p = 0; p < RO.qsz.size(); ++p) mine[1] += varint_len(0) + RO.qsz[p];
 		if (T)
 		{
-			std::vector<uint64_t> all(8 * (size_t)world);
-			ck(ctx, T->all_gather_host(mine, 8, all.data()), "all-gather of the stream sizes");
-			uint64_t dna_all = 0; for (uint32_t r = 0; r < world; ++r) { if (r == rank) RO.dna_base = dna_all; dna_all += all[8 * r]; }
-			uint64_t q = dna_all; for (uint32_t r = 0; r < world; ++r) { if (r == rank) RO.qual_base = q; q += all[8 * r + 1]; }
-			for (uint32_t r = 0; r < world; ++r) for (int s = 0; s < 2; ++s) { RO.dig_all[s].reads += all[8 * r + 2 + 3 * s]; RO.dig_all[s].symbols += all[8 * r + 3 + 3 * s]; RO.dig_all[s].sum += all[8 * r + 4 + 3 * s]; }
+			std::vector<uint64_t> all(n_mine * (size_t)world);
+			ck(ctx, T->all_gather_host(mine, n_mine, all.data()), "all-gather of the stream sizes");
+			uint64_t dna_all = 0; for (uint32_t r = 0; r < world; ++r) { if (r == rank) RO.dna_base = dna_all; dna_all += all[n_mine * r]; }
+			uint64_t q = dna_all; for (uint32_t r = 0; r < world; ++r) { if (r == rank) RO.qual_base = q; q += all[n_mine * r + 1]; }
+			for (uint32_t r = 0; r < world; ++r) for (int s = 0; s < n_dig; ++s) { RO.dig_all[s].reads += all[n_mine * r + 2 + 3 * s]; RO.dig_all[s].symbols += all[n_mine * r + 3 + 3 * s]; RO.dig_all[s].sum += all[n_mine * r + 4 + 3 * s]; }
 		}
 		else
 		{	// independent domains run one after the other: a domain's parts follow those of the domains before it
@@ -276,10 +282,11 @@ int run_compress_multi(const Options& O)
 	ar.add(s_dom, dom.data(), dom.size(), 0);
 	if (O.digest)
 	{	// the ranks' digests added: as rank 0 gathered them with the byte counts, or (independent domains: nothing is exchanged) from the domains' own
-		cl_digest dd[2] = { out[0].dig_all[0], out[0].dig_all[1] };
-		if (independent) for (int s = 0; s < 2; ++s) { dd[s] = cl_digest{ 0, 0, 0 }; for (uint32_t r = 0; r < world; ++r) { dd[s].reads += out[r].dig[s].reads; dd[s].symbols += out[r].dig[s].symbols; dd[s].sum += out[r].dig[s].sum; } }
+		cl_digest dd[3] = { out[0].dig_all[0], out[0].dig_all[1], out[0].dig_all[2] };
+		if (independent) for (int s = 0; s < 3; ++s) { dd[s] = cl_digest{ 0, 0, 0 }; for (uint32_t r = 0; r < world; ++r) { dd[s].reads += out[r].dig[s].reads; dd[s].symbols += out[r].dig[s].symbols; dd[s].sum += out[r].dig[s].sum; } }
 		if (dd[0].reads != n || dd[0].symbols != total) die("internal: the content digest did not see every read");
-		add_digest(ar, dd[0], with_qual && O.P.qual_mode != 8 ? &dd[1] : nullptr, hdr.digest);
+		if (digest_values && (dd[2].reads != n || dd[2].symbols != total)) die("internal: the content digest did not see every read");
+		add_digest(ar, dd[0], with_qual && O.P.qual_mode != 8 ? &dd[1] : nullptr, hdr.digest, digest_values ? &dd[2] : nullptr);
 	}
 	finish_archive(ar, O, R, tot);
 	if (use_rccl) rccl.destroy_all();

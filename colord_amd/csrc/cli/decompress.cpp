@@ -119,7 +119,7 @@ int run_info(int argc, char** argv)
 		I.version_major, I.version_minor, I.version_patch, (unsigned long long)I.total_bytes, (unsigned long long)I.total_bases, I.total_reads, asctime(localtime(&t)), I.command_line.c_str());
 	ar.close();
 	DigestSet stored;                                                          // archives written with --digest: the content digests they must decode to
-	if (read_hipdigest(argv[2], stored) > 0) for (int i = 0; i < 3; ++i) if ((stored.flags >> i) & 1) fprintf(stderr, "content digest: %s\n", stored.line(i).c_str());
+	if (read_hipdigest(argv[2], stored) > 0) for (int j = 0; j < 4; ++j) if (const int i = DigestSet::in_order(j); (stored.flags >> i) & 1) fprintf(stderr, "content digest: %s\n", stored.line(i).c_str());
 	return 0;
 }
 
@@ -146,8 +146,9 @@ struct Decoded { uint64_t n_rec = 0; DigestSet computed; size_t domains = 0, at_
 // stream threads each, as for a whole archive — into a file of its own next to the output; the files are then joined in order.  The ids
 // come from one pass over the `header` stream that all workers share.  false: the archive is not of that kind (the caller then decodes
 // it as one stream).  out_path empty: nothing is written (`colord_hip check`).  With want_digest every worker digests its domain's reads
-// at their indices in the whole input and the partial digests are added; the header digest is the shared pass's.
-static bool decode_domains(const std::string& arc, const std::string& genome, const std::string& out_path, int max_threads, bool want_digest, Decoded& D)
+// at their indices in the whole input and the partial digests are added; the header digest is the shared pass's.  want_values: the
+// qual-values digest of the quality bytes too.
+static bool decode_domains(const std::string& arc, const std::string& genome, const std::string& out_path, int max_threads, bool want_digest, bool want_values, Decoded& D)
 {
 	size_t K = 0; bool is_fastq = true;
 	{ RecordStream probe(arc, genome); if (!probe.independent_domains() || probe.n_domains() < 2) return false; K = probe.n_domains(); is_fastq = probe.is_fastq(); }
@@ -166,6 +167,7 @@ static bool decode_domains(const std::string& arc, const std::string& genome, co
 			{
 				RecordStream r(arc, genome, (int)d, &hc);
 				if (want_digest) r.enable_digest();
+				if (want_values) r.enable_digest_values();
 				r.prefetch();
 				{ static std::mutex hm; std::lock_guard<std::mutex> l(hm); if (ht.joinable()) ht.join(); }
 				if (!hc.err.empty()) throw std::runtime_error("header stream: " + hc.err);
@@ -187,7 +189,7 @@ static bool decode_domains(const std::string& arc, const std::string& genome, co
 	for (auto& t : th) t.join();
 	if (ht.joinable()) ht.join();
 	for (size_t d = 0; d < K; ++d) if (!errs[d].empty()) { if (writing) for (auto& t : tmp) remove(t.c_str()); die("domain " + std::to_string(d) + ": " + errs[d]); }
-	for (size_t d = 0; d < K; ++d) { D.n_rec += n_rec[d]; D.computed.flags |= dig[d].flags; D.computed.add(0, dig[d].d[0]); D.computed.add(1, dig[d].d[1]); }
+	for (size_t d = 0; d < K; ++d) { D.n_rec += n_rec[d]; D.computed.flags |= dig[d].flags; D.computed.add(0, dig[d].d[0]); D.computed.add(1, dig[d].d[1]); D.computed.add(3, dig[d].d[3]); }
 	if (want_digest) { D.computed.flags |= 4u; D.computed.add(2, hc.digest); }
 	D.domains = K; D.at_a_time = T;
 	if (!writing) return true;
@@ -210,17 +212,18 @@ static bool decode_domains(const std::string& arc, const std::string& genome, co
 // The records of an archive in file order, written to out_path (empty: decoded only).  remove_on_error: a decoding error takes the
 // output file with it (an archive whose content digest is being checked leaves no half-written or unconfirmed file behind).
 // gpu >= 0 (`--gpu N`): the quality stream of an archive with `hipqdomains` is decoded on that device; any other archive on the host as ever
-static void decode_archive(const std::string& arc, const std::string& genome, const std::string& out_path, int dom_threads, bool want_digest, bool remove_on_error, int gpu, Decoded& D)
+static void decode_archive(const std::string& arc, const std::string& genome, const std::string& out_path, int dom_threads, bool want_digest, bool want_values, bool remove_on_error, int gpu, Decoded& D)
 {
 	auto fail = [&](const std::string& m) { if (remove_on_error && !out_path.empty()) (void)remove(out_path.c_str()); die(m); };
 	const char* why_host = "--gpu: the archive has no `hipqdomains` stream (it was written without --qual-domain-symbols): its quality stream is one dependent chain per domain and is decoded on the host";
-	try { if (decode_domains(arc, genome, out_path, dom_threads, want_digest, D)) { if (gpu >= 0) fprintf(stderr, "colord_hip: %s\n", why_host); return; } } catch (const std::exception& e) { fail(e.what()); }
+	try { if (decode_domains(arc, genome, out_path, dom_threads, want_digest, want_values, D)) { if (gpu >= 0) fprintf(stderr, "colord_hip: %s\n", why_host); return; } } catch (const std::exception& e) { fail(e.what()); }
 	bool write_ok = true;
 	DeviceQualDecoder dev(gpu);                                                // (outlives the record stream, whose quality thread calls it)
 	try
 	{
 		RecordStream rs(arc, genome);
 		if (want_digest) rs.enable_digest();
+		if (want_values) rs.enable_digest_values();
 		if (gpu >= 0)
 		{
 			if (rs.n_qual_domains())
@@ -274,7 +277,8 @@ int run_decompress(int argc, char** argv)
 	DigestSet stored; const int have = ignore_digest ? 0 : read_hipdigest(pos[0], stored);
 	if (have < 0) die("the archive's `hipdigest` stream is not one this build reads (--ignore-digest decodes without the check)");
 	Decoded D;
-	decode_archive(pos[0], genome, pos[1], dom_threads, have > 0, have > 0, gpu, D);
+	// (the qual-values digest only where the archive stores one: --digest-values)
+	decode_archive(pos[0], genome, pos[1], dom_threads, have > 0, have > 0 && ((stored.flags >> 3) & 1), have > 0, gpu, D);
 	if (have > 0)
 	{
 		const std::string bad = digest_mismatch(stored, D.computed);
@@ -303,11 +307,12 @@ int run_check(int argc, char** argv)
 	if (pos.size() != 1) { fprintf(stderr, "usage: colord_hip check [-G reference_genome.fa] [--gpu N] archive.colord\n"); return 1; }
 	DigestSet stored; const int have = read_hipdigest(pos[0], stored);
 	Decoded D;
-	decode_archive(pos[0], genome, "", dom_threads, true, false, gpu, D);
+	decode_archive(pos[0], genome, "", dom_threads, true, true, false, gpu, D);
 	for (int i = 0; i < 3; ++i) printf("%s\n", D.computed.line(i).c_str());
+	if ((D.computed.flags >> 3) & 1) printf("%s\n", D.computed.line(3).c_str());      // (any archive with a coded quality stream, the reference's included)
 	if (have == 0) { printf("no content digest is stored in this archive (written without --digest); %llu records decode\n", (unsigned long long)D.n_rec); return 0; }
 	if (have < 0) { printf("the archive's `hipdigest` stream is not one this build reads\n"); return 1; }
-	for (int i = 0; i < 3; ++i) if ((stored.flags >> i) & 1) printf("stored %s\n", stored.line(i).c_str());
+	for (int j = 0; j < 4; ++j) if (const int i = DigestSet::in_order(j); (stored.flags >> i) & 1) printf("stored %s\n", stored.line(i).c_str());
 	const std::string bad = digest_mismatch(stored, D.computed);
 	if (!bad.empty()) { printf("content digest mismatch: %s\n", bad.c_str()); return 1; }
 	printf("content digest: ok (%s)\n", stored.names().c_str());

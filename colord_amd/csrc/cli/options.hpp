@@ -38,6 +38,7 @@ struct Options {
 	bool verify_scripts = false;                    // --verify-scripts: cl_ctx_set_verify on every compressor's context
 	bool verify_streams = false;                    // --verify-streams: cl_ctx_set_verify_streams on every compressor's context
 	bool digest = false;                            // --digest: content digests of the input (cl_ctx_set_digest; ids on the host) in a `hipdigest` stream
+	bool digest_values = false;                     // --digest-values: --digest and the qual-values digest (cl_ctx_set_digest_values); `hipdigest` version 2
 	uint64_t qual_domain_symbols = 0;               // --qual-domain-symbols N: the quality models start afresh about every N symbols (cl_compressor_set_qual_domain_symbols; stream `hipqdomains`)
 	int gpus = 1; std::vector<int> gpu_list; std::string transport = "rccl";   // --gpus N [--gpu-list a,b,..] [--transport rccl|host]: reads sharded over N GPUs (run_compress_multi)
 	Preset P{}; QDef qd;                            // resolved by parse_options: the preset of source and priority with the options laid over it, the quality thresholds / representatives
@@ -70,7 +71,12 @@ inline void usage()
 		"                     are stored in the archive (stream `hipdigest`, 80 bytes; the reference's decompressor ignores it).  `colord_hip decompress` recomputes them from what it\n"
 		"                     decodes: a difference is a message naming the stream, no output file and exit 1 (--ignore-digest decodes regardless); `colord_hip check` decodes without\n"
 		"                     writing and prints them.  Same digest with any --part-symbols, --stream-input, --domains, --gpus.  Covered: input -> ... -> decoded symbols; the quality\n"
-		"                     VALUES made from the symbols (-D values, error diffusion of *-avg) are not.  Cost: one pass over 1.4 bytes per base per chunk (not measured on a GPU yet)\n"
+		"                     VALUES made from the symbols (-D values, error diffusion of *-avg) are covered by --digest-values.  Cost: one pass over 1.4 bytes per base per chunk (not measured on a GPU yet)\n"
+		"  --digest-values    --digest, and a fourth digest, qual-values: the quality VALUES every record must decode to (org: the value; *-fix: the -D value of its bin; *-avg, avg:\n"
+		"                     the error diffusion of the bin's average, as integers), made on the device from the input qualities alone and stored with the other three (`hipdigest`\n"
+		"                     version 2, 104 bytes).  `colord_hip decompress` / `check` digest the quality bytes as they are handed to the writer, whichever decoder made them (host, or\n"
+		"                     --gpu): the hole --digest leaves between the decoded symbols and the quality line is closed.  With -q none or FASTA input there are no values: as --digest.\n"
+		"                     Cost: one more pass over the quality bytes per chunk, two in the *-avg modes (not measured on a GPU yet)\n"
 		"  --qual-domain-symbols N   model domains of the QUALITY stream alone: its adaptive models start afresh at the first part boundary at which a domain holds N coded\n"
 		"                     symbols, and the starts are recorded (stream `hipqdomains`).  `colord_hip decompress --gpu N` / `check --gpu N` then decode the domains side by\n"
 		"                     side on the device, one lane each; without --gpu they decode on the host as one chain that starts afresh at every domain.  The k-mer set, the\n"
@@ -135,6 +141,7 @@ inline Options parse_options(int argc, char** argv)
 		else if (a == "--verify-scripts") O.verify_scripts = true;
 		else if (a == "--verify-streams") O.verify_streams = true;
 		else if (a == "--digest") O.digest = true;
+		else if (a == "--digest-values") O.digest = O.digest_values = true;
 		else if (a == "--parse-threads") { O.parse_threads = atoi(need(i).c_str()); if (O.parse_threads < 1 || O.parse_threads > 256) die("--parse-threads must be in [1, 256]"); }
 		else if (a == "-h" || a == "--help") { usage(); exit(0); }
 		else if (!a.empty() && a[0] == '-' && a.size() > 1) die("unknown option " + a);

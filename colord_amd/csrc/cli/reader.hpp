@@ -175,6 +175,8 @@ class RecordStream {
 	bool is_qdomain_start(size_t part) const { return std::binary_search(qdomains.begin(), qdomains.end(), QualDomain{ part, 0 }, [](const QualDomain& a, const QualDomain& b) { return a.first_part < b.first_part; }); }
 	// content digest (digest_stream.hpp): each stream thread digests what it decodes, read by read from the first read it decodes on
 	bool want_digest = false; cl_digest dig_dna{ 0, 0, 0 }, dig_qual{ 0, 0, 0 }, dig_hdr{ 0, 0, 0 };
+	// qual-values: the quality thread digests the quality BYTES of every part as it hands them on to the writer — whichever decoder made them
+	bool want_values = false; cl_digest dig_qval{ 0, 0, 0 };
 	uint64_t first_read_index() const { return only_domain >= 0 ? dom_read[only_domain] : 0; }
 	size_t part_begin() const { return only_domain >= 0 ? (size_t)dom_part[only_domain] : 0; }
 	size_t part_end() const { return only_domain >= 0 && (size_t)only_domain + 1 < dom_part.size() ? (size_t)dom_part[only_domain + 1] : ar.n_parts(s_dna); }
@@ -197,7 +199,13 @@ public:
 	// before the first record is asked for: the stream threads digest what they decode.  digests(): after next() has returned false —
 	// dna, qual (flag off without a quality stream or in mode none, which decodes nothing) and header (not with external ids: theirs is the cache's)
 	void enable_digest() { if (!started) want_digest = true; }
-	DigestSet digests() const { DigestSet s; s.flags = 1u | (fastq && M.qual_mode != 8 ? 2u : 0u) | (ext_hdr ? 0u : 4u); s.d[0] = dig_dna; s.d[1] = dig_qual; s.d[2] = dig_hdr; return s; }
+	// with enable_digest: also the qual-values digest (flag off without a coded quality stream, as for qual)
+	void enable_digest_values() { if (!started) want_values = true; }
+	DigestSet digests() const
+	{
+		DigestSet s; s.flags = 1u | (fastq && M.qual_mode != 8 ? 2u : 0u) | (ext_hdr ? 0u : 4u) | (want_values && fastq && M.qual_mode != 8 ? 8u : 0u);
+		s.d[0] = dig_dna; s.d[1] = dig_qual; s.d[2] = dig_hdr; s.d[3] = dig_qval; return s;
+	}
 	// `hipqdomains`: how many model domains the quality stream has of its own (0: none — one chain, or the domains of `hipdomains`)
 	size_t n_qual_domains() const { return qdomains.size(); }
 	// before the first record is asked for, archives with `hipqdomains` only: the quality thread no longer decodes part by part — it
@@ -340,6 +348,14 @@ inline void RecordStream::start()
 		if (cl_qual_decoder_create(&qpar, &q) != CL_OK) { err_qual = "cl_qual_decoder_create"; }
 		if (q && want_digest && cl_qual_decoder_set_digest(q, 1, first_read_index()) != CL_OK) { err_qual = "cl_qual_decoder_set_digest"; cl_qual_decoder_free(q); q = nullptr; }
 		ReadPart x; std::vector<uint8_t> in; uint64_t meta = 0; size_t p = part_begin(); const size_t p_first = p;
+		// the ONE place where decoded qualities leave for the writer, behind the host decoder and behind the batches of the device decoder:
+		// `first` = the part's first read in the whole input
+		const bool values = want_digest && want_values && M.qual_mode != 8;
+		auto hand_on = [&](ReadPart& y, uint64_t first) {
+			if (values && !dg_qual_ascii_host(y.quals.data(), y.off.data(), y.off.size() - 1, first, &dig_qval)) throw std::runtime_error("more reads than the content digest can index");
+			y.bases.clear(); y.bases.shrink_to_fit();
+			q_quals.push(std::move(y));
+		};
 		try {
 		if (q && qual_batches)
 		{	// whole model domains, many at a time (set_qual_batch_decoder)
@@ -347,11 +363,12 @@ inline void RecordStream::start()
 			auto flush = [&]() {
 				if (B.parts.empty()) return;
 				qual_batches(qpar, B, want_digest && M.qual_mode != 8 ? &dig_qual : nullptr);
+				uint64_t first = B.first_read;
 				for (ReadPart& y : B.parts)
 				{
 					if (y.quals.size() != y.bases.size()) throw std::runtime_error("the batch decoder left a part without its qualities");
-					y.bases.clear(); y.bases.shrink_to_fit();
-					q_quals.push(std::move(y));
+					const uint64_t nr = y.off.size() - 1;
+					hand_on(y, first); first += nr;
 				}
 				B = QualBatch(); B.first_read = g;
 			};
@@ -379,12 +396,12 @@ inline void RecordStream::start()
 		{
 			if (!ar.part(s_qual, p, in, meta)) { err_qual = "cannot read a `qual` part"; break; }
 			if (is_qdomain_start(p)) check_qdomain_read(p, reads_before);
+			const uint64_t part_first = reads_before;
 			reads_before += x.off.size() - 1;
 			if (p > p_first && (is_domain_start(p) || is_qdomain_start(p))) cl_qual_decoder_new_domain(q);
 			x.quals.resize(x.bases.size());
 			if (cl_qual_decode_part(q, in.data(), in.size(), x.bases.data(), x.off.data(), (uint32_t)(x.off.size() - 1), x.quals.data()) != CL_OK) { err_qual = "corrupt `qual` part"; break; }
-			x.bases.clear(); x.bases.shrink_to_fit();
-			q_quals.push(std::move(x));
+			hand_on(x, part_first);
 			++p;
 		}
 		} catch (const std::exception& e) { err_qual = std::string("corrupt `qual` part (") + e.what() + ")"; }

@@ -348,6 +348,8 @@ struct cl_ctx {
 	std::atomic<uint64_t> verified_stream_parts{ 0 }, verified_stream_symbols{ 0 }, verified_stream_bytes{ 0 };   // what the coders on this context have checked so
 	bool digest = false;                         // cl_ctx_set_digest: cl_compress_shard / cl_compressor_encode on this context digest their input (digest.hip)
 	cl_digest digest_dna{ 0, 0, 0 }, digest_qual{ 0, 0, 0 };   // the totals so far (owner thread only)
+	bool digest_values = false;                  // cl_ctx_set_digest_values: the same calls digest the quality VALUES of their input (k_qual_values)
+	cl_digest digest_qval{ 0, 0, 0 };
 	std::map<std::string, KernelTime> times;     // per-kernel accumulated HIP-event time of the last API call
 	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
 	std::vector<double> pending_bytes, pending_cells;

@@ -1,5 +1,6 @@
 // digest.hip — the content digests of a chunk on the device (digest.hpp): cl_digest_bases over the 2-bit arena,
-// cl_digest_quals over the quality bytes, both from the INPUT alone; their host counterparts; the pipeline's hook (digest_chunk).
+// cl_digest_quals and cl_digest_qual_values / cl_qual_values over the quality bytes, all from the INPUT alone; their host counterparts;
+// the pipeline's hooks (digest_chunk, digest_values_chunk).
 //
 // Shape of both kernels (that of k_qual_symbols and k_es_expand): one wave per read, four reads per 256-thread block; the lanes stride
 // over the read's arena words / over 8-byte groups of its quality bytes, so a wave reads 512 contiguous bytes a step; the terms of W are
@@ -67,6 +68,29 @@ struct DigestQualArg { uint32_t mode, n_bins, navg, per_base; uint64_t map8[12];
 __device__ inline uint64_t load_q8(const uint8_t* __restrict__ q, uint64_t i) { uint64_t v; __builtin_memcpy(&v, q + i, 8); return v; }
 __device__ inline uint32_t q_value(uint32_t byte) { const uint32_t q = byte - 33u; return q > 95u ? 0u : q; }     // (outside Phred+33 0..95: as k_qual_symbols, which makes cl_qual_encode refuse the input)
 
+// Pass one of the averaging modes, for k_digest_quals and k_qual_values: the wave's per-bin integer sums and counts of the read q[0 .. len),
+// then a[t] = the two average bytes of bin t as one integer (dg_avg16; 0 for an empty bin and for t >= bins).  one_bin (avg): every base in bin 0.
+__device__ inline void bin_averages(const uint8_t* s_map, bool one_bin, uint32_t bins, const uint8_t* __restrict__ q, uint64_t len, uint32_t lane, uint32_t (&a)[5])
+{
+	uint32_t sum[5] = { 0, 0, 0, 0, 0 }, cnt[5] = { 0, 0, 0, 0, 0 };
+	auto count = [&](uint32_t byte) {
+		const uint32_t v = q_value(byte), b = one_bin ? 0u : s_map[v];
+#pragma unroll
+		for (uint32_t t = 0; t < 5; ++t) if (b == t) { sum[t] += v; cnt[t] += 1; }
+	};
+	for (uint64_t i = 8ull * lane; i < len; i += 512)
+	{
+		if (i + 8 <= len) { const uint64_t v = load_q8(q, i);
+#pragma unroll
+			for (uint32_t k = 0; k < 8; ++k) count((uint32_t)(v >> (8 * k)) & 0xffu); }
+		else for (uint64_t j = i; j < len; ++j) count(q[j]);
+	}
+#pragma unroll
+	for (uint32_t t = 0; t < 5; ++t) { sum[t] = wave_sum(sum[t]); cnt[t] = wave_sum(cnt[t]); }
+#pragma unroll
+	for (uint32_t t = 0; t < 5; ++t) a[t] = t < bins ? dg_avg16(sum[t], one_bin ? len : (uint64_t)cnt[t]) : 0u;
+}
+
 __global__ __launch_bounds__(256) void k_digest_quals(DigestQualArg cfg, const uint8_t* __restrict__ quals, const uint64_t* __restrict__ qoff,
                                                      uint32_t n_reads, uint64_t first_read, unsigned long long* __restrict__ slots)
 {
@@ -86,37 +110,13 @@ __global__ __launch_bounds__(256) void k_digest_quals(DigestQualArg cfg, const u
 		uint64_t a_lo = 0, a_hi = 0;
 		if (navg)
 		{
-			uint32_t sum[5] = { 0, 0, 0, 0, 0 }, cnt[5] = { 0, 0, 0, 0, 0 };
-			auto count = [&](uint32_t byte) {
-				const uint32_t v = q_value(byte), b = cfg.mode == 7 ? 0u : s_map[v];
+			uint32_t a[5];
+			bin_averages(s_map, cfg.mode == 7, cfg.mode == 7 ? 1u : cfg.n_bins, q, len, lane, a);
 #pragma unroll
-				for (uint32_t t = 0; t < 5; ++t) if (b == t) { sum[t] += v; cnt[t] += 1; }
-			};
-			for (uint64_t i = 8ull * lane; i < len; i += 512)
+			for (uint32_t t = 0; t < 5; ++t)
 			{
-				if (i + 8 <= len) { const uint64_t v = load_q8(q, i);
-#pragma unroll
-					for (uint32_t k = 0; k < 8; ++k) count((uint32_t)(v >> (8 * k)) & 0xffu); }
-				else for (uint64_t j = i; j < len; ++j) count(q[j]);
-			}
-#pragma unroll
-			for (uint32_t t = 0; t < 5; ++t) { sum[t] = wave_sum(sum[t]); cnt[t] = wave_sum(cnt[t]); }
-			if (cfg.mode == 7)
-			{
-				const double avg = len ? (double)sum[0] / (double)len : 0.0;
-				const uint32_t a = (uint32_t)(avg * 256);
-				a_lo = (uint64_t)(a >> 8) | ((uint64_t)(a & 0xff) << 8);
-			}
-			else
-			{
-#pragma unroll
-				for (uint32_t t = 0; t < 5; ++t) if (t < cfg.n_bins)
-				{
-					const double avg = cnt[t] ? (double)sum[t] / (double)cnt[t] : 0.0;
-					const uint32_t a = (uint32_t)(avg * 256);
-					const uint64_t two = (uint64_t)(a >> 8) | ((uint64_t)(a & 0xff) << 8);
-					if (t < 4) a_lo |= two << (16 * t); else a_hi = two;
-				}
+				const uint64_t two = (uint64_t)(a[t] >> 8) | ((uint64_t)(a[t] & 0xff) << 8);
+				if (t < 4) a_lo |= two << (16 * t); else a_hi = two;
 			}
 		}
 		// the read's symbols: the average bytes, then (per_base) one symbol a base; word i = symbols 8 i .. 8 i + 7
@@ -146,6 +146,112 @@ __global__ __launch_bounds__(256) void k_digest_quals(DigestQualArg cfg, const u
 		}
 		const uint64_t W = wave_sum64(acc);
 		term = dg_term(dg_read(W, n, DG_QUAL), first_read + r); syms = n;
+	}
+	block_add(term, syms, slots);
+}
+
+// ---- qual-values (digest.hpp, kind 4): the values the decoders will make of a read's quality symbols, from the INPUT qualities -----
+// tab8: the 96-entry table of dg_value_layout — the value itself (org, *-fix) or the bin (diffuse: *-avg, avg)
+struct QualValueArg { uint32_t diffuse, bins; uint64_t tab8[12]; };
+__device__ inline uint64_t wave_incl_scan64(uint64_t v, uint32_t lane)
+{
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) { const uint64_t t = (uint64_t)__shfl_up((unsigned long long)v, d, 64); if ((int)lane >= d) v += t; }
+	return v;
+}
+__device__ inline void store_q8(uint8_t* __restrict__ p, uint64_t v) { __builtin_memcpy(p, &v, 8); }             // one unaligned 8-byte store inside the read
+constexpr uint64_t DG_ASCII8 = 0x2121212121212121ULL;                           // + 33 on each of eight values <= 222: no carry between the bytes
+
+// One wave per read, four reads a block.  Lane l of step s holds group i = 64 s + l: the bytes 8 i .. 8 i + 7 of the read (one 8-byte load;
+// the last, partial group byte by byte), which become the read's digest word i and, under STORE, eight bytes of `values` (value + 33, at the
+// offsets of qoff).  org / *-fix: a table look-up per byte.  Diffusing modes: pass one gives A per bin (bin_averages); then per step every
+// lane counts its bytes per bin into one word of five 10-bit fields (a step holds <= 512 bytes), ONE 64-bit wave scan gives it the rank of
+// its first byte in every bin within the step, the bins' totals of the steps before are five wave-uniform 64-bit counters, and the lane
+// walks its bytes in registers: k = carried + before + 1, 2, ..; v = dg_diffuse(A, k).  Every loop bound is known before the loop; nothing
+// outside [qoff[r], qoff[r + 1]) is loaded or stored for read r.
+template<bool STORE>
+__global__ __launch_bounds__(256) void k_qual_values(QualValueArg cfg, const uint8_t* __restrict__ quals, const uint64_t* __restrict__ qoff, uint32_t n_reads, uint64_t first_read,
+                                                    uint8_t* __restrict__ values, unsigned long long* __restrict__ slots)
+{
+	__shared__ uint64_t s_tab8[12];
+#pragma unroll
+	for (uint32_t t = 0; t < 12; ++t) if (threadIdx.x == t) s_tab8[t] = cfg.tab8[t];
+	__syncthreads();
+	const uint8_t* s_tab = (const uint8_t*)s_tab8;
+	const uint32_t r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+	uint64_t term = 0, syms = 0;
+	if (r < n_reads)                                                            // (wave-uniform)
+	{
+		const uint64_t qb = qoff[r], len = qoff[r + 1] - qb;
+		const uint8_t* __restrict__ q = quals + qb;                              // this read's bytes: q[0 .. len)
+		uint8_t* __restrict__ out = STORE ? values + qb : nullptr;               // its values: out[0 .. len)
+		const uint64_t words = (len + 7) / 8, steps = (words + 63) / 64;
+		uint64_t acc = 0;
+		// the group's word (its values, low byte first) into the digest and, under STORE, into out[j0 .. j0 + nb)
+		auto emit = [&](uint64_t w, uint64_t i, uint32_t nb) {
+			acc += dg_word(w, i);
+			if (STORE)
+			{
+				const uint64_t a = w + DG_ASCII8;
+				if (nb == 8) store_q8(out + 8 * i, a); else for (uint32_t k = 0; k < nb; ++k) out[8 * i + k] = (uint8_t)(a >> (8 * k));
+			}
+		};
+		if (!cfg.diffuse)
+		{
+			for (uint64_t i = lane; i < words; i += 64)
+			{
+				const uint64_t j0 = 8 * i;
+				uint64_t w = 0; uint32_t nb = 8;
+				if (j0 + 8 <= len)
+				{
+					const uint64_t v = load_q8(q, j0);
+#pragma unroll
+					for (uint32_t k = 0; k < 8; ++k) w |= (uint64_t)s_tab[q_value((uint32_t)(v >> (8 * k)) & 0xffu)] << (8 * k);
+				}
+				else { nb = (uint32_t)(len - j0); for (uint32_t k = 0; k < nb; ++k) w |= (uint64_t)s_tab[q_value(q[j0 + k])] << (8 * k); }
+				emit(w, i, nb);
+			}
+		}
+		else
+		{
+			uint32_t A[5];
+			bin_averages(s_tab, cfg.bins == 1, cfg.bins, q, len, lane, A);
+			uint64_t carried[5] = { 0, 0, 0, 0, 0 };                               // per bin: the read's bases of the steps before (wave-uniform)
+			for (uint64_t s = 0; s < steps; ++s)                                    // (wave-uniform: every lane takes part in the scan)
+			{
+				const uint64_t i = 64 * s + lane, j0 = 8 * i;
+				uint64_t v = 0; uint32_t nb = 0;
+				if (j0 + 8 <= len) { v = load_q8(q, j0); nb = 8; }
+				else if (j0 < len) { nb = (uint32_t)(len - j0); for (uint32_t k = 0; k < nb; ++k) v |= (uint64_t)q[j0 + k] << (8 * k); }
+				uint32_t bins = 0; uint64_t mine = 0;                               // the bins of the lane's bytes, 3 bits each; its count per bin, 10 bits each
+#pragma unroll
+				for (uint32_t k = 0; k < 8; ++k) if (k < nb)
+				{
+					const uint32_t b = s_tab[q_value((uint32_t)(v >> (8 * k)) & 0xffu)];
+					bins |= b << (3 * k); mine += 1ULL << (10 * b);
+				}
+				const uint64_t incl = wave_incl_scan64(mine, lane), before = incl - mine;
+				const uint64_t total = (uint64_t)__shfl((unsigned long long)incl, 63, 64);
+				uint64_t k_of[5];
+#pragma unroll
+				for (uint32_t t = 0; t < 5; ++t) k_of[t] = carried[t] + ((before >> (10 * t)) & 1023u);
+				uint64_t w = 0;
+#pragma unroll
+				for (uint32_t k = 0; k < 8; ++k) if (k < nb)
+				{
+					const uint32_t b = (bins >> (3 * k)) & 7u;
+					uint64_t kk = 0; uint32_t a = 0;
+#pragma unroll
+					for (uint32_t t = 0; t < 5; ++t) if (b == t) { kk = ++k_of[t]; a = A[t]; }
+					w |= (uint64_t)dg_diffuse(a, kk) << (8 * k);
+				}
+				if (nb) emit(w, i, nb);
+#pragma unroll
+				for (uint32_t t = 0; t < 5; ++t) carried[t] += (total >> (10 * t)) & 1023u;
+			}
+		}
+		const uint64_t W = wave_sum64(acc);
+		term = dg_term(dg_read(W, len, DG_QVAL), first_read + r); syms = len;
 	}
 	block_add(term, syms, slots);
 }
@@ -220,6 +326,70 @@ extern "C" cl_status cl_ctx_digest(const cl_ctx* c, cl_digest* dna, cl_digest* q
 	if (qual) *qual = c->digest_qual;
 	return CL_OK;
 }
+// ---- qual-values --------------------------------------------------------------------------------------------------------------------
+namespace {
+// both entry points: acc (digest) and / or d_values (the ASCII values)
+cl_status qual_values_run(cl_ctx* ctx, const char* who, const cl_qual_params* qparams, const cl_reads* R, const uint8_t* d_quals, const uint64_t* d_qual_off,
+                          uint64_t first_read, uint8_t* d_values, cl_digest* acc)
+{
+	DigestValueLayout V;
+	if (qparams->mode == 8) return CL_OK;                                       // none: nothing is coded, nothing is digested
+	if (!dg_value_layout(qparams, V)) return cl_fail(ctx, CL_E_INVALID, std::string(who) + ": mode 0..8 with the thresholds of its bins and, for *-fix, a -D value (<= 222) for every bin");
+	if (!dg_range_ok(first_read, R->n_reads)) return cl_fail(ctx, CL_E_INVALID, std::string(who) + ": first_read + n_reads exceeds 2^63");
+	if (!R->n_reads) return CL_OK;
+	if (!d_quals || !d_qual_off) return cl_fail(ctx, CL_E_INVALID, std::string(who) + ": null argument");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	QualValueArg A; A.diffuse = V.diffuse; A.bins = V.bins;
+	memcpy(A.tab8, V.tab, 96);
+	DigestRun run; CL_TRY(digest_begin(ctx, run));
+	// bytes: every quality byte once, twice where the averages need a pass of their own, the offsets, and the values where they are stored
+	const double bytes = (V.diffuse ? 2.0 : 1.0) * R->total_bases + 8.0 * R->n_reads + (d_values ? 1.0 * R->total_bases : 0.0);
+	if (d_values) LAUNCHB(ctx, bytes, k_qual_values<true>, grid_for(R->n_reads, 4), 256, A, d_quals, d_qual_off, R->n_reads, first_read, d_values, run.slots.p);
+	else LAUNCHB(ctx, bytes, k_qual_values<false>, grid_for(R->n_reads, 4), 256, A, d_quals, d_qual_off, R->n_reads, first_read, (uint8_t*)nullptr, run.slots.p);
+	cl_digest d{ 0, 0, 0 };
+	CL_TRY(digest_collect(ctx, run, R->n_reads, &d));
+	if (acc) { acc->reads += d.reads; acc->symbols += d.symbols; acc->sum += d.sum; }
+	return CL_OK;
+}
+} // namespace
+
+extern "C" cl_status cl_digest_qual_values(cl_ctx* ctx, const cl_qual_params* qparams, const cl_reads* R, const uint8_t* d_quals, const uint64_t* d_qual_off,
+                                           uint64_t first_read, cl_digest* acc)
+{
+	if (!ctx || !qparams || !R || !acc) return cl_fail(ctx, CL_E_INVALID, "cl_digest_qual_values: null argument");
+	return qual_values_run(ctx, "cl_digest_qual_values", qparams, R, d_quals, d_qual_off, first_read, nullptr, acc);
+}
+extern "C" cl_status cl_qual_values(cl_ctx* ctx, const cl_qual_params* qparams, const cl_reads* R, const uint8_t* d_quals, const uint64_t* d_qual_off,
+                                    uint8_t* d_values, uint64_t cap)
+{
+	if (!ctx || !qparams || !R) return cl_fail(ctx, CL_E_INVALID, "cl_qual_values: null argument");
+	if (qparams->mode == 8) return cl_fail(ctx, CL_E_INVALID, "cl_qual_values: mode none codes no quality values");
+	if (!R->n_reads) return CL_OK;
+	if (!d_qual_off) return cl_fail(ctx, CL_E_INVALID, "cl_qual_values: null argument");
+	// the values go to the offsets of d_qual_off: its last one is what d_values must hold (read back before anything is launched)
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	uint64_t end = 0;
+	HIP_TRY(ctx, hipMemcpyAsync(&end, d_qual_off + R->n_reads, 8, hipMemcpyDeviceToHost, cl_launch_stream(ctx)));
+	HIP_TRY(ctx, hipStreamSynchronize(cl_launch_stream(ctx)));
+	if (cap < end) return cl_fail(ctx, CL_E_CAPACITY, "cl_qual_values: d_values holds " + std::to_string(cap) + " bytes, the offsets end at " + std::to_string(end));
+	if (end && !d_values) return cl_fail(ctx, CL_E_INVALID, "cl_qual_values: null argument");
+	return qual_values_run(ctx, "cl_qual_values", qparams, R, d_quals, d_qual_off, 0, d_values, nullptr);
+}
+extern "C" cl_status cl_qual_values_host(const cl_qual_params* qparams, const uint8_t* h_quals, const uint64_t* h_off, uint64_t n, uint8_t* h_values)
+{
+	return dg_qual_values_host(qparams, h_quals, h_off, n, h_values, 0, nullptr) ? CL_OK : CL_E_INVALID;
+}
+extern "C" cl_status cl_digest_qual_values_host(const uint8_t* h_ascii_quals, const uint64_t* h_off, uint64_t n, uint64_t first_read, cl_digest* acc)
+{
+	return dg_qual_ascii_host(h_ascii_quals, h_off, n, first_read, acc) ? CL_OK : CL_E_INVALID;
+}
+extern "C" void cl_ctx_set_digest_values(cl_ctx* c, int on) { if (c) c->digest_values = on != 0; }
+extern "C" cl_status cl_ctx_digest_values(const cl_ctx* c, cl_digest* out)
+{
+	if (!c || !out) return CL_E_INVALID;
+	*out = c->digest_qval;
+	return CL_OK;
+}
 // Internal (driver.hip, stream.hip): the digests of one chunk of the input, whose first read is read `first_read`, into the context's totals
 cl_status digest_chunk(cl_ctx* ctx, const cl_reads* reads, const cl_qual_params* qparams, const uint8_t* d_quals, const uint64_t* d_base_off, uint64_t first_read)
 {
@@ -228,5 +398,14 @@ cl_status digest_chunk(cl_ctx* ctx, const cl_reads* reads, const cl_qual_params*
 	if (qparams) CL_TRY(cl_digest_quals(ctx, qparams, reads, d_quals, d_base_off, first_read, &q));
 	ctx->digest_dna.reads += d.reads; ctx->digest_dna.symbols += d.symbols; ctx->digest_dna.sum += d.sum;
 	ctx->digest_qual.reads += q.reads; ctx->digest_qual.symbols += q.symbols; ctx->digest_qual.sum += q.sum;
+	return CL_OK;
+}
+// The same for the qual-values digest alone (cl_ctx_set_digest_values); nothing without a quality stream
+cl_status digest_values_chunk(cl_ctx* ctx, const cl_reads* reads, const cl_qual_params* qparams, const uint8_t* d_quals, const uint64_t* d_base_off, uint64_t first_read)
+{
+	if (!qparams) return CL_OK;
+	cl_digest v{ 0, 0, 0 };
+	CL_TRY(cl_digest_qual_values(ctx, qparams, reads, d_quals, d_base_off, first_read, &v));
+	ctx->digest_qval.reads += v.reads; ctx->digest_qval.symbols += v.symbols; ctx->digest_qval.sum += v.sum;
 	return CL_OK;
 }

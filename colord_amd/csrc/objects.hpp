@@ -60,6 +60,8 @@ cl_status cl_es_verify_at(cl_ctx* ctx, const cl_reads* reads, const cl_reads* re
 // digest.hip (cl_ctx_set_digest): the dna digest of a chunk whose first read is read `first_read` of the input and, with qparams, its qual
 // digest, added to the context's totals; on the context's stream, from the input arena and quality bytes alone
 cl_status digest_chunk(cl_ctx* ctx, const cl_reads* reads, const cl_qual_params* qparams, const uint8_t* d_quals, const uint64_t* d_base_off, uint64_t first_read);
+// (cl_ctx_set_digest_values): the qual-values digest of the same chunk, from the input quality bytes alone (nothing with qparams null or mode none)
+cl_status digest_values_chunk(cl_ctx* ctx, const cl_reads* reads, const cl_qual_params* qparams, const uint8_t* d_quals, const uint64_t* d_base_off, uint64_t first_read);
 const cl_qual_params* cl_qual_coder_params(const cl_qual_coder* q);     // qual.hip: the parameters the coder was created with
 
 // the DNA coder's state-independent half ahead of time (dna.hip): lookahead.hip walks the NEXT chunk's tuples from the hook that

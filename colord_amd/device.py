@@ -53,6 +53,7 @@ class _OrderedLib:
     _HOST_ONLY = ("cl_last_error", "cl_ctx_kernel_times", "cl_ctx_last_kernel_ms", "cl_ctx_set_timing", "cl_ref_accept", "cl_ctx_set_verify", "cl_ctx_verified",
                   "cl_compressor_verified", "cl_ctx_set_verify_streams", "cl_ctx_verified_streams", "cl_compressor_verified_streams",
                   "cl_ctx_set_digest", "cl_ctx_digest", "cl_compressor_digest", "cl_digest_bases_host", "cl_digest_bytes_host", "cl_qual_decoder_set_digest", "cl_qual_decoder_digest",
+                  "cl_ctx_set_digest_values", "cl_ctx_digest_values", "cl_compressor_digest_values", "cl_qual_values_host", "cl_digest_qual_values_host",
                   "cl_qual_coder_domains", "cl_compressor_qual_domains")
 
     def __init__(self, lib, device):
@@ -161,6 +162,45 @@ class Context:
         quals, qual_off = quals.contiguous(), qual_off.contiguous()
         _check(self, self.lib.cl_digest_quals(self.h, C.byref(prm), reads.h, quals.data_ptr() if quals.numel() else None, qual_off.data_ptr(), first_read, C.byref(acc)))
         return acc.triple()
+
+    def set_digest_values(self, on: bool = True):
+        """cl_ctx_set_digest_values: compress_shard() and compressors of this context digest the quality VALUES their input will decode to."""
+        self.lib.cl_ctx_set_digest_values(self.h, int(bool(on)))
+
+    def digest_values(self):
+        """cl_ctx_digest_values: (reads, symbols, sum) of the qual-values digest so far on this context."""
+        d = N.Digest()
+        _check(None, self.lib.cl_ctx_digest_values(self.h, C.byref(d)))
+        return d.triple()
+
+    @staticmethod
+    def _qual_params(mode, fwd, rev):
+        prm = N.QualParams()
+        prm.mode, prm.source, prm.level, prm.n_fwd, prm.n_rev = mode, 0, 1, len(fwd), len(rev)
+        for i, v in enumerate(fwd):
+            prm.fwd[i] = v
+        for i, v in enumerate(rev):
+            prm.rev[i] = v
+        return prm
+
+    def digest_qual_values(self, reads: "Reads", quals: torch.Tensor, qual_off: torch.Tensor, mode: int, fwd=(), rev=(), first_read: int = 0, acc: "N.Digest | None" = None):
+        """cl_digest_qual_values: the qual-values digest of what a decoder of `mode` (thresholds fwd, -D values rev) will write for the reads, added to acc."""
+        prm = self._qual_params(mode, fwd, rev)
+        acc = N.Digest() if acc is None else acc
+        quals, qual_off = quals.contiguous(), qual_off.contiguous()
+        _check(self, self.lib.cl_digest_qual_values(self.h, C.byref(prm), reads.h, quals.data_ptr() if quals.numel() else None, qual_off.data_ptr(), first_read, C.byref(acc)))
+        return acc.triple()
+
+    def qual_values(self, reads: "Reads", quals: torch.Tensor, qual_off: torch.Tensor, mode: int, fwd=(), rev=(), out: "torch.Tensor | None" = None):
+        """cl_qual_values: the ASCII quality bytes a decoder of `mode` will write for the reads, at the offsets of qual_off; `out` (a uint8
+        tensor on the device, made here when None) may be larger than the last offset — one that is smaller raises CL_E_CAPACITY."""
+        prm = self._qual_params(mode, fwd, rev)
+        quals, qual_off = quals.contiguous(), qual_off.contiguous()
+        if out is None:
+            out = torch.empty(int(qual_off[-1]) if qual_off.numel() else 0, dtype=torch.uint8, device=quals.device)
+        _check(self, self.lib.cl_qual_values(self.h, C.byref(prm), reads.h, quals.data_ptr() if quals.numel() else None, qual_off.data_ptr(),
+                                             out.data_ptr() if out.numel() else None, out.numel()))
+        return out
 
     # ---- arena ----
     def pack_reads(self, codes: torch.Tensor, offsets: torch.Tensor, ascii: bool = False) -> "Reads":
@@ -684,6 +724,12 @@ class Compressor(_Obj):
         d, q = N.Digest(), N.Digest()
         _check(None, self.ctx.lib.cl_compressor_digest(self.h, C.byref(d), C.byref(q)))
         return d.triple(), q.triple()
+
+    def digest_values(self):
+        """cl_compressor_digest_values: (reads, symbols, sum) of the qual-values digest of the chunks encoded so far (Context.set_digest_values)."""
+        d = N.Digest()
+        _check(None, self.ctx.lib.cl_compressor_digest_values(self.h, C.byref(d)))
+        return d.triple()
 
     def set_qual_domain_symbols(self, n: int):
         """cl_compressor_set_qual_domain_symbols: model domains of the quality stream; before the first encode / prepare call."""

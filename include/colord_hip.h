@@ -94,6 +94,13 @@ typedef struct cl_digest { uint64_t reads, symbols, sum; } cl_digest;
  * cl_ctx_digest: the totals so far (either pointer may be null). */
 void cl_ctx_set_digest(cl_ctx* ctx, int on);
 cl_status cl_ctx_digest(const cl_ctx* ctx, cl_digest* dna, cl_digest* qual);
+/* Opt-in digest of the quality VALUES (off by default: one flag test, no launch, no allocation, every output byte the same; a flag
+ * of its own, independent of cl_ctx_set_digest).  While it is on, the same calls add, next to the other two and before the coders
+ * start, the qual-values digest of the chunk (cl_digest_qual_values) at its global read index to the context's total — nothing
+ * without a quality stream or in mode none.  The quality parameters must carry the -D values (rev) for *-fix: CL_E_INVALID if not.
+ * cl_ctx_digest_values: the total so far. */
+void cl_ctx_set_digest_values(cl_ctx* ctx, int on);
+cl_status cl_ctx_digest_values(const cl_ctx* ctx, cl_digest* out);
 
 /* ---- read arena: replaces read_t / read_pack_t (src/colord/utils.h:366-376, in_reads.cpp:24-42) -- */
 /* d_codes: concatenated bases, 1 byte per base; either codes 0..4 (ascii=0) or ASCII ACGTN, upper
@@ -327,6 +334,27 @@ cl_status cl_digest_quals(cl_ctx* ctx, const cl_qual_params* qparams, const cl_r
  * = the bytes [h_off[i], h_off[i + 1]) of h_bytes (ids followed by their '+' byte; explicit symbol sequences). */
 cl_status cl_digest_bases_host(const uint8_t* h_codes, const uint64_t* h_off, uint64_t n, uint64_t first_read, cl_digest* acc);
 cl_status cl_digest_bytes_host(uint32_t kind, const uint8_t* h_bytes, const uint64_t* h_off, uint64_t n, uint64_t first_read, cl_digest* acc);
+/* The qual-values digest (kind 4): what the quality DECODER will write for the reads, stated from the input qualities.  Per read one
+ * byte per base in read order, the decoded value minus 33, eight to a word little-endian; n = bases.  With q = input byte - 33
+ * (outside 0..95: 0) and bin = the bin of q under the -T thresholds — org: q; *-fix: rev[bin], the -D values
+ * (quality_coder_impl.cpp:313-435); *-avg and avg (one bin): the k-th base of a bin in the read gets
+ * floor(k A / 256) - floor((k - 1) A / 256), A = the bin's two average bytes as one integer — the decoders' error diffusion
+ * `as += avg; v = (uint32)(as - qs); qs += v` (quality_coder_impl.cpp:506-559,800-849; CQualityCoder's decode, quality_coder.cpp:605-657),
+ * exact in IEEE double because every partial sum is a multiple of 1/256; none: nothing at all (*acc is left as it is).  CL_E_INVALID:
+ * thresholds that do not fit the mode, *-fix without a -D value for every bin, a -D value above 222.  Nothing outside
+ * [d_qual_off[r], d_qual_off[r + 1]) is read for read r. */
+cl_status cl_digest_qual_values(cl_ctx* ctx, const cl_qual_params* qparams, const cl_reads* reads, const uint8_t* d_quals, const uint64_t* d_qual_off,
+                                uint64_t first_read, cl_digest* acc);
+/* The values themselves: d_values[d_qual_off[r] + i] = the ASCII byte (value + 33) the decoder will write for base i of read r; nothing
+ * outside [d_qual_off[r], d_qual_off[r + 1]) is written for read r.  cap: the bytes of d_values (CL_E_CAPACITY below the last offset,
+ * d_qual_off[n_reads], before anything is launched).  Mode none: CL_E_INVALID. */
+cl_status cl_qual_values(cl_ctx* ctx, const cl_qual_params* qparams, const cl_reads* reads, const uint8_t* d_quals, const uint64_t* d_qual_off,
+                         uint8_t* d_values, uint64_t cap);
+/* On the HOST.  cl_qual_values_host: the same values from input qualities (read i = [h_off[i], h_off[i + 1]) of h_quals) into h_values
+ * at the same offsets.  cl_digest_qual_values_host: the qual-values digest of DECODED quality lines (ASCII, as a decoder returns
+ * them), read i being read first_read + i of the input, added to *acc. */
+cl_status cl_qual_values_host(const cl_qual_params* qparams, const uint8_t* h_quals, const uint64_t* h_off, uint64_t n, uint8_t* h_values);
+cl_status cl_digest_qual_values_host(const uint8_t* h_ascii_quals, const uint64_t* h_off, uint64_t n, uint64_t first_read, cl_digest* acc);
 
 /* ---- a14 + a16: CDNACoder / CEntrComprReads (dna_coder.{h,cpp}, entr_read.h:56-80) --------------------- */
 typedef struct cl_dna_coder cl_dna_coder;
@@ -476,6 +504,8 @@ cl_status cl_compressor_verified_streams(const cl_compressor* c, uint64_t* parts
 /* cl_ctx_digest of the compressor's context: the digests of the chunks encoded so far (cl_ctx_set_digest); read indices are global:
  * this rank's first read (cl_compressor_info) + the reads of its chunks before */
 cl_status cl_compressor_digest(const cl_compressor* c, cl_digest* dna, cl_digest* qual);
+/* cl_ctx_digest_values of the compressor's context (cl_ctx_set_digest_values) */
+cl_status cl_compressor_digest_values(const cl_compressor* c, cl_digest* out);
 
 /* cl_qual_coder_set_domain_symbols / cl_qual_coder_domains of the compressor's quality coder.  The setting must be made before the
  * first cl_compressor_encode or cl_compressor_prepare_parts call (CL_E_INVALID afterwards, and without a quality stream); the `dna`
