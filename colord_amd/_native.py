@@ -74,6 +74,7 @@ _SIG = {
     "cl_ctx_set_timing": (None, [_P, C.c_int]),
     "cl_ctx_set_verify": (None, [_P, C.c_int]),
     "cl_ctx_verified": (C.c_int32, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cl_ctx_gap_paths": (C.c_int32, [_P, C.POINTER(C.c_uint64), C.c_uint32]),
     "cl_ctx_set_verify_streams": (None, [_P, C.c_int]),
     "cl_ctx_verified_streams": (C.c_int32, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cl_compressor_verified_streams": (C.c_int32, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

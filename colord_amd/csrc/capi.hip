@@ -135,6 +135,12 @@ extern "C" cl_status cl_ctx_verified(const cl_ctx* c, uint64_t* reads, uint64_t*
 	if (bases) *bases = b;
 	return CL_OK;
 }
+extern "C" cl_status cl_ctx_gap_paths(const cl_ctx* c, uint64_t* out, uint32_t cap)
+{
+	if (!c || (!out && cap)) return CL_E_INVALID;
+	for (uint32_t i = 0; i < cap && i < 11; ++i) out[i] = c->gap_paths[i];
+	return CL_OK;
+}
 extern "C" void cl_ctx_set_verify_streams(cl_ctx* c, int on) { if (c) c->verify_streams = on != 0; }
 extern "C" cl_status cl_ctx_verified_streams(const cl_ctx* c, uint64_t* parts, uint64_t* symbols, uint64_t* bytes)
 {

@@ -1086,6 +1086,7 @@ extern "C" cl_status cl_encode_reads(cl_ctx* ctx, const cl_reads* reads, const c
 	if (n_packs && (h_pack_bounds[0] != 0 || h_pack_bounds[n_packs] != nr)) return cl_fail(ctx, CL_E_INVALID, "cl_encode_reads: packs must cover the arena");
 	if (max_rec > 8 || c > 16) return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_encode_reads: max_rec <= 8 and c <= 16");
 	*n_out = 0;
+	for (uint64_t& x : ctx->gap_paths) x = 0;
 	if (!nr) return CL_OK;
 	ArenaV A{ reads->packed.p, reads->word_off.p, reads->lens.p }, R{ refs->packed.p, refs->word_off.p, refs->lens.p };
 	AnchorsV AV{ cl_anchors_n_cands(anchors), cl_anchors_cands(anchors), cl_anchors_cand_offsets(anchors), cl_anchors_data(anchors) };
@@ -1336,6 +1337,7 @@ extern "C" cl_status cl_encode_reads(cl_ctx* ctx, const cl_reads* reads, const c
 					HIP_TRY(ctx, hipStreamSynchronize(st));
 					list = todo.p;
 				}
+				if (n_list) ++ctx->gap_paths[10];                                     // a further round with larger pools
 				per_lane *= 8; max_lanes = std::max<uint32_t>(max_lanes / 8, 64);
 			}
 			return CL_OK;
@@ -1362,6 +1364,11 @@ extern "C" cl_status cl_encode_reads(cl_ctx* ctx, const cl_reads* reads, const c
 		}
 		else if (hb[8] > hb[7]) CL_TRY(run_large(ids.p + hb[7], hb[8] - hb[7], 1.25 * (double)h_cb[7]));   // (COLORD_HIP_NO_TEAM_ALIGN)
 		if (n_team_redo) CL_TRY(run_large(team_redo.p, n_team_redo, 0.0));
+		for (uint32_t cls = 0; cls < N_CLASSES; ++cls) ctx->gap_paths[cls] += hb[cls + 1] - hb[cls];
+		ctx->gap_paths[8] += n_quad_redo; ctx->gap_paths[9] += n_team_redo;
+		if (getenv("COLORD_HIP_GAP_DEBUG"))
+			fprintf(stderr, "[gaps] level %u: per class %u %u %u %u %u %u %u %u; quad -> wave %u, giant -> wave %u; wave-pool redo rounds of the call so far %llu\n", lv, hb[1] - hb[0], hb[2] - hb[1],
+				hb[3] - hb[2], hb[4] - hb[3], hb[5] - hb[4], hb[6] - hb[5], hb[7] - hb[6], hb[8] - hb[7], n_quad_redo, n_team_redo, (unsigned long long)ctx->gap_paths[10]);
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->side));                           // the small gaps are through
 		if (getenv("COLORD_HIP_GAP_SHAPES"))
 		{	// diagnostic: shapes and edit distances of the aligned gaps by class — what a band (edlib.cpp:192-212) would save, what fits LDS

@@ -54,7 +54,7 @@ class _OrderedLib:
                   "cl_compressor_verified", "cl_ctx_set_verify_streams", "cl_ctx_verified_streams", "cl_compressor_verified_streams",
                   "cl_ctx_set_digest", "cl_ctx_digest", "cl_compressor_digest", "cl_digest_bases_host", "cl_digest_bytes_host", "cl_qual_decoder_set_digest", "cl_qual_decoder_digest",
                   "cl_ctx_set_digest_values", "cl_ctx_digest_values", "cl_compressor_digest_values", "cl_qual_values_host", "cl_digest_qual_values_host",
-                  "cl_qual_coder_domains", "cl_compressor_qual_domains")
+                  "cl_qual_coder_domains", "cl_compressor_qual_domains", "cl_ctx_gap_paths")
 
     def __init__(self, lib, device):
         self._lib, self._device, self._cache = lib, device, {}
@@ -123,6 +123,14 @@ class Context:
         r, b = C.c_uint64(0), C.c_uint64(0)
         _check(None, self.lib.cl_ctx_verified(self.h, C.byref(r), C.byref(b)))
         return r.value, b.value
+
+    def gap_paths(self):
+        """cl_ctx_gap_paths of the last encode_reads(): {"classes": gaps per size class 0..7, "quad_to_wave", "giant_to_wave",
+        "wave_redo_rounds"} summed over the recursion levels."""
+        out = (C.c_uint64 * 11)()
+        _check(None, self.lib.cl_ctx_gap_paths(self.h, out, 11))
+        v = [int(x) for x in out]
+        return {"classes": v[:8], "quad_to_wave": v[8], "giant_to_wave": v[9], "wave_redo_rounds": v[10]}
 
     def set_verify_streams(self, on: bool = True):
         """cl_ctx_set_verify_streams: the DNA and quality coders of this context decode every coded part on the device against the

@@ -82,6 +82,12 @@ cl_status cl_ctx_verified(const cl_ctx* ctx, uint64_t* reads, uint64_t* bases);
  * its own counts there; cl_compressor_verified_streams adds them up). */
 void cl_ctx_set_verify_streams(cl_ctx* ctx, int on);
 cl_status cl_ctx_verified_streams(const cl_ctx* ctx, uint64_t* parts, uint64_t* symbols, uint64_t* bytes);
+/* Which aligner took the gaps of the LAST cl_encode_reads on this context, summed over its recursion levels (host counts the call
+ * keeps anyway: no launch, no allocation).  Writes min(cap, 11) values: out[0..7] gaps per size class (0 trivial, 1..4 small with that
+ * many 64-row blocks, 5 four per wave, 6 a wave each, 7 giant: tile jobs), out[8] class-5 gaps the wave kernel redid (distance beyond
+ * the band), out[9] giant gaps the tile jobs handed back to the wave kernel, out[10] further rounds of the wave kernel with larger
+ * pools.  COLORD_HIP_GAP_DEBUG prints the same per level. */
+cl_status cl_ctx_gap_paths(const cl_ctx* ctx, uint64_t* out, uint32_t cap);
 /* Content digest: reads and symbols counted, and a 64-bit sum over the reads that depends on every symbol, on its place
  * in its read and on the read's index g in the whole input — and on nothing else (not on parts, chunks, lanes, domains or ranks).
  * Digests of disjoint sets of reads add field by field (wrapping), in any order. */

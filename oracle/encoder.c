@@ -912,3 +912,15 @@ done:
 	free(b.p);
 	return n;
 }
+
+/* GetEditDist (encoder.cpp:1255-1283) of ONE gap, as EncodePart calls it: where = 0 the read's left flank (frag_no 0), 1 an inner
+ * gap, 2 the right flank (frag_no n_fragments - 1).  The canonical script goes to out when cap suffices; returns its length. */
+size_t orc_gap_script(const uint8_t* ref, uint32_t nr, const uint8_t* enc, uint32_t ne, int where, char* out, size_t cap, uint32_t* dist)
+{
+	edres_t r = get_edit_dist(ref, nr, enc, ne, (uint32_t)where, 3);
+	const size_t n = r.es.n;
+	if (out && cap >= n && n) memcpy(out, r.es.p, n);
+	if (dist) *dist = r.dist;
+	str_free(&r.es);
+	return n;
+}

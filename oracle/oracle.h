@@ -104,6 +104,9 @@ uint32_t orc_encoder_candidates(orc_encoder*, const uint8_t* read, uint32_t len,
                                 const uint64_t* common, const uint32_t* common_off, uint32_t* out_cand, uint32_t* out_anchors, size_t cap_anchors, size_t* n_anchors);
 size_t orc_encoder_encode(orc_encoder*, const uint8_t* read, uint32_t len, int has_n, const uint32_t* neighbours, uint32_t n_nb,
                           const uint64_t* common, const uint32_t* common_off, uint8_t* out, size_t cap, uint32_t* n_tuples);
+/* a10 only: GetEditDist (encoder.cpp:1255-1283) of one gap.  where: 0 left flank, 1 inner, 2 right flank.  The canonical script
+ * (refactored, with the left flank's leading deletions) is written to out when cap suffices; returns its length, *dist = editDist. */
+size_t orc_gap_script(const uint8_t* ref, uint32_t nr, const uint8_t* enc, uint32_t ne, int where, char* out, size_t cap, uint32_t* dist);
 
 /* ---- a11: the decision logarithm (utils.h:800-810), host libm — the pin of the device's log2 ------- */
 void orc_estimator_logs(const uint32_t* count, const uint32_t* total, size_t n, double* out);

@@ -73,6 +73,8 @@ def lib():
         L.orc_encoder_candidates.argtypes = [C.c_void_p, u8p, C.c_uint32, u32p, C.c_uint32, C.c_void_p, C.c_void_p, u32p, u32p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.orc_encoder_encode.restype = C.c_size_t
         L.orc_encoder_encode.argtypes = [C.c_void_p, u8p, C.c_uint32, C.c_int, u32p, C.c_uint32, C.c_void_p, C.c_void_p, u8p, C.c_size_t, C.POINTER(C.c_uint32)]
+        L.orc_gap_script.restype = C.c_size_t
+        L.orc_gap_script.argtypes = [u8p, C.c_uint32, u8p, C.c_uint32, C.c_int, u8p, C.c_size_t, C.POINTER(C.c_uint32)]
         _LIB = L
     return _LIB
 
@@ -233,6 +235,7 @@ class Encoder:
     """CEncoder for one encoder thread: per-pack estimator, reference reads added in reference-id order."""
     def __init__(self, a, k, f, source, frac_always=0.9, frac_min=0.5, max_matches_mult=10.0, cost_mult=1.0, min_part_alt=64, max_rec=3, min_anchors=1):
         self.h = lib().orc_encoder_new(a, k, f, source, frac_always, frac_min, max_matches_mult, cost_mult, min_part_alt, max_rec, min_anchors)
+        self._ref_lens = []
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -242,6 +245,7 @@ class Encoder:
     def add_ref(self, bases):
         b = np.ascontiguousarray(bases, np.uint8)
         lib().orc_encoder_add_ref(self.h, b if len(b) else np.zeros(1, np.uint8), len(b))
+        self._ref_lens.append(len(b))
 
     def new_pack(self):
         lib().orc_encoder_new_pack(self.h)
@@ -282,7 +286,23 @@ class Encoder:
             if len(call) == 0:
                 call = np.zeros(1, np.uint64)
             cptr, coff_ptr = call.ctypes.data, coff.ctypes.data
-        out = np.zeros(2 * len(r) + 64, np.uint8)
+        # a script deletes at most every symbol of every candidate once (a gap of many reference symbols against few of the read)
+        out = np.zeros(2 * len(r) + 64 + sum(self._ref_lens[int(i)] + 8 for i in neighbours if int(i) < len(self._ref_lens)), np.uint8)
         nt = C.c_uint32(0)
         n = lib().orc_encoder_encode(self.h, r if len(r) else np.zeros(1, np.uint8), len(r), int(has_n), nb, len(neighbours), cptr, coff_ptr, out, len(out), C.byref(nt))
+        if n > len(out):
+            raise RuntimeError(f"oracle: tuple stream of {n} bytes does not fit {len(out)}")
         return out[:n].tobytes(), nt.value
+
+
+GAP_LEFT, GAP_INNER, GAP_RIGHT = 0, 1, 2
+
+
+def gap_script(ref, enc, where: int):
+    """GetEditDist of one gap (where: GAP_LEFT / GAP_INNER / GAP_RIGHT): (canonical script as bytes, edit distance)."""
+    r, e = np.ascontiguousarray(ref, np.uint8), np.ascontiguousarray(enc, np.uint8)
+    out = np.zeros(len(r) + len(e) + 1, np.uint8)
+    d = C.c_uint32(0)
+    one = np.zeros(1, np.uint8)
+    n = lib().orc_gap_script(r if len(r) else one, len(r), e if len(e) else one, len(e), where, out, len(out), C.byref(d))
+    return out[:n].tobytes(), d.value

@@ -46,5 +46,23 @@ def test_shw_end_before_target_start():
     enc = O.Encoder(16, 20, 12, 0)
     ref = np.array([0] * 40, np.uint8)
     enc.add_ref(ref)
-    # not reachable through the public entry without anchors; covered end-to-end by s6m_ont read 309 above
-    assert True
+    # reachable through the public entry: a read whose flank shares nothing with its reference (tests/gapshapes.py), and directly
+    # through the gap's own entry.  A query of a multiple of 64 symbols has no such end position and consumes reference symbols.
+    import gapshapes as G
+    cases = [c for c in G.CASES if c["name"].startswith("shw_nothing")]
+    assert sorted({c["ne"] for c in cases}) == [63, 64, 65, 128] and {c["where"] for c in cases} == {"L", "R"}
+    for c in cases:
+        p = G.make_parts(c)
+        letters = bytes(b"ACGT"[b] for b in p["Ge"])
+        es, dist = O.gap_script(p["Gr"], p["Ge"], G.WHERE_CODE[c["where"]])
+        if c["ne"] % 64:
+            assert dist == c["ne"] and es == (b"D" * c["nr"] if c["where"] == "L" else b"") + letters, c["name"]
+        else:
+            assert dist == c["ne"] and sum(es.count(x) for x in b"XYZ") > 0 and not any(x in es for x in b"M"), c["name"]
+        ref, read = G.make_pair(c)
+        e = O.Encoder(G.A_LEN, G.K_LEN, G.MODULO, 0, **G.ACCEPT_ALL)
+        e.add_ref(ref)
+        e.new_pack()
+        first, whole = G.decode_tuples(e.encode(read, False, [0])[0])
+        core = b"M" * (c["cores"][1] if c["where"] == "L" else c["cores"][0])
+        assert first == 10 and whole == (es + core if c["where"] == "L" else core + es), c["name"]
