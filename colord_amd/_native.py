@@ -195,6 +195,7 @@ _SIG = {
     "cl_encode_reads": (C.c_int32, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, _P, C.c_uint32, _P, C.c_uint64, _P, _P, C.POINTER(C.c_uint64)]),
     "cl_dna_coder_create": (C.c_int32, [_P, C.c_uint32, C.c_int32, C.c_uint32, C.POINTER(_P)]),
     "cl_dna_coder_free": (None, [_P]),
+    "cl_dna_coder_model": (C.c_int32, [_P, C.c_uint32, C.c_uint64, _P]),
     "cl_dna_encode": (C.c_int32, [_P, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
     "cl_sort_u64": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32]),
     "cl_sort_u64_u32": (C.c_int32, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32]),

@@ -141,6 +141,11 @@ extern "C" cl_status cl_ctx_gap_paths(const cl_ctx* c, uint64_t* out, uint32_t c
 	for (uint32_t i = 0; i < cap && i < 11; ++i) out[i] = c->gap_paths[i];
 	return CL_OK;
 }
+extern "C" cl_status cl_dna_coder_model(const cl_dna_coder* d, uint32_t family, uint64_t context, uint32_t* out)
+{
+	if (!d || !out) return CL_E_INVALID;
+	return cl_dna_model_read(d, family, context, out);
+}
 extern "C" void cl_ctx_set_verify_streams(cl_ctx* c, int on) { if (c) c->verify_streams = on != 0; }
 extern "C" cl_status cl_ctx_verified_streams(const cl_ctx* c, uint64_t* parts, uint64_t* symbols, uint64_t* bytes)
 {

@@ -1298,6 +1298,20 @@ cl_status cl_dna_batch_types(cl_ctx* ctx, const uint8_t* d_es, const uint64_t* d
 }
 void cl_dna_walked_free(DnaWalked* W) { delete W; }
 void cl_dna_set_ahead(cl_dna_coder* D, DnaWalked* W) { if (D) D->ahead.reset(W); else delete W; }
+// cl_dna_coder_model (capi.hip): counters and total of one model as the last finished cl_dna_encode left them.  Batches evolved ahead
+// (cl_dna_evolve_ahead) have changed the models already: refused while one is held.
+cl_status cl_dna_model_read(const cl_dna_coder* D, uint32_t family, uint64_t context, uint32_t* out)
+{
+	cl_ctx* ctx = D->ctx;
+	const FamTab& f = D->ft;
+	if (family >= N_FAM || context >= f.n_ctx[family]) return cl_fail(ctx, CL_E_INVALID, "cl_dna_coder_model: no such family or context");
+	if (!D->evolved.empty()) return cl_fail(ctx, CL_E_INVALID, "cl_dna_coder_model: a batch evolved ahead has changed the models");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	const uint32_t n = f.n_sym[family] + 1;
+	HIP_TRY(ctx, hipMemcpy(out, D->state.p + f.state_base[family] + context * n, (size_t)n * 4, hipMemcpyDeviceToHost));
+	return CL_OK;
+}
 void cl_dna_coder_state(const cl_dna_coder* D, uint32_t* prev_types, uint32_t* read_id) { if (prev_types) *prev_types = D->prev_types; if (read_id) *read_id = D->cur_read_id; }
 
 // Internal (lookahead.hip): the walk of the batch that FOLLOWS the one being coded, from inside cl_dna_encode's before_tail hook.

@@ -521,7 +521,7 @@ class Context:
     def dna_coder(self, max_alt_refs: int, level: int, start_read_id: int = 0) -> "DnaCoder":
         h = N._P()
         _check(self, self.lib.cl_dna_coder_create(self.h, max_alt_refs, level, start_read_id, C.byref(h)))
-        return DnaCoder(self, h)
+        return DnaCoder(self, h, max_alt_refs)
 
     def sort_u64(self, keys: torch.Tensor, vals: torch.Tensor | None = None, begin_bit=0, end_bit=64):
         if vals is None:
@@ -789,6 +789,11 @@ class Compressor(_Obj):
 
 class DnaCoder(_Obj):
     _free = "cl_dna_coder_free"
+    N_SYM = (3, 2, 2, 32, 256, 4, 5, 256, 0, 24, 256, 256, 8)          # symbols per model family (0: max_alt_refs)
+
+    def __init__(self, ctx, h, max_alt_refs):
+        super().__init__(ctx, h)
+        self.max_alt_refs = max_alt_refs
 
     def encode(self, refs: "Reads", es: torch.Tensor, es_off: torch.Tensor, es_ntuples: torch.Tensor, part_bounds):
         """Returns (payload bytes tensor on device, list of part sizes)."""
@@ -804,6 +809,12 @@ class DnaCoder(_Obj):
                                    pb.ctypes.data, n_parts, out.data_ptr(), cap, sizes.ctypes.data, C.byref(n))
         _check(ctx, st)
         return out[:n.value], [int(x) for x in sizes[:n_parts]]
+
+    def model(self, family: int, context: int) -> np.ndarray:
+        """cl_dna_coder_model: the counters and, last, the total of one adaptive model after the last encode()."""
+        out = np.zeros(257, np.uint32)
+        _check(self.ctx, self.ctx.lib.cl_dna_coder_model(self.h, family, context, out.ctypes.data))
+        return out[:(self.N_SYM[family] or self.max_alt_refs) + 1].copy()
 
 
 class Anchors(_Obj):

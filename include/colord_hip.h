@@ -368,6 +368,13 @@ typedef struct cl_dna_coder cl_dna_coder;
  * persists across cl_dna_encode calls; start_read_id seeds cur_read_id. */
 cl_status cl_dna_coder_create(cl_ctx* ctx, uint32_t max_alt_refs, int32_t level, uint32_t start_read_id, cl_dna_coder** out);
 void cl_dna_coder_free(cl_dna_coder* d);
+/* Test access: out[0 .. n_sym) = the counters and out[n_sym] = the total of one adaptive model, as the last finished cl_dna_encode
+ * left them (all ones before its first symbol).  family: 0 read type (3 symbols), 1 orientation (2), 2 seen (2), 3 length bits (32),
+ * 4 length data (256), 5 symbols (4), 6 symbols with N (5), 7 read id (256), 8 short read id (max_alt_refs), 9 anchor length (24),
+ * 10 local skip (256), 11 distant skip (256), 12 tuple type (8).  context: the reference's context value of that family where the
+ * reference symbol is a base (positions past a reference read's end are kept apart).  A read-only copy after a wait for the
+ * context's stream; CL_E_INVALID for an unknown family or context, or while a batch evolved ahead is held. */
+cl_status cl_dna_coder_model(const cl_dna_coder* d, uint32_t family, uint64_t context, uint32_t* out);
 /* CEntrComprReads::Compress for a batch of whole parts.  d_es: the reads' tuple streams (es_t byte layout,
  * utils.h:56-273) back to back, d_es_off: n_reads+1 byte offsets, d_es_ntuples: es_t::size() per read.
  * refs: arena whose read i is reference read i (CReferenceReads order).  Parts [h_part_bounds[p],

@@ -19,8 +19,8 @@ struct orc_dna {
 	uint64_t mask_tuple, mask_symbol;
 	uint64_t ctx_read_type, ctx_rev_comp, ctx_tuple_type, ctx_symbol;
 	int cur_ref_delta;
-	/* per-read orientation cache (uo_rev_comp) */
-	int rc_ids[64]; int rc_val[64]; int n_rc;
+	/* per-read orientation cache (uo_rev_comp, dna_coder.h:89): an unbounded map in the reference, so it grows here as well */
+	int* rc_ids; int n_rc, cap_rc;
 	orc_ctxmap m_read_type, m_rev_comp, m_seen, m_len_bits, m_len_data, m_symbols, m_symbols_n, m_read_id, m_read_id_short,
 		m_anchor_len, m_skip_local, m_skip_distant, m_tuple_type;
 	refread_t* refs; size_t n_refs, cap_refs;
@@ -68,7 +68,7 @@ void orc_dna_free(orc_dna* d)
 		&d->m_read_id, &d->m_read_id_short, &d->m_anchor_len, &d->m_skip_local, &d->m_skip_distant, &d->m_tuple_type };
 	for (size_t i = 0; i < sizeof(ms) / sizeof(ms[0]); ++i) orc_ctxmap_free(ms[i]);
 	for (size_t i = 0; i < d->n_refs; ++i) free(d->refs[i].b);
-	free(d->refs); free(d->out.p); free(d);
+	free(d->refs); free(d->rc_ids); free(d->out.p); free(d);
 }
 /* CReferenceReads::Add (reference_reads.h:209-212); reads are kept as plain codes here */
 void orc_dna_add_ref(orc_dna* d, const uint8_t* bases, uint32_t len)
@@ -120,7 +120,8 @@ static void enc_rev_comp(orc_dna* d, int read_id, int rc)                       
 {
 	for (int i = 0; i < d->n_rc; ++i) if (d->rc_ids[i] == read_id) return;
 	orc_encode_sym(&d->enc, &d->m_rev_comp, d->ctx_rev_comp, (uint32_t)rc, -1, -1);
-	if (d->n_rc < 64) { d->rc_ids[d->n_rc] = read_id; d->rc_val[d->n_rc] = rc; ++d->n_rc; }
+	if (d->n_rc == d->cap_rc) { d->cap_rc = d->cap_rc ? 2 * d->cap_rc : 64; d->rc_ids = (int*)realloc(d->rc_ids, (size_t)d->cap_rc * sizeof(int)); }
+	d->rc_ids[d->n_rc++] = read_id;                                              /* (the cached value is not needed to encode) */
 	d->ctx_rev_comp = ((d->ctx_rev_comp << 2) + (uint64_t)rc) & 0xf;
 }
 static void enc_tuple_type(orc_dna* d, uint32_t type, uint32_t ref_symbol, uint32_t last, int first)   /* :651-710 */
@@ -338,6 +339,21 @@ void orc_dna_encode(orc_dna* d, const uint8_t* es, size_t n_bytes, uint32_t n_tu
 		last_type = type;
 	}
 	++d->cur_read_id;
+}
+
+/* Test access: counters [0, n_sym) and total [n_sym] of one model, all ones if the context was never coded.  family: the order of
+ * the device's F_* enumeration (dna.hip).  Returns n_sym, 0 for an unknown family or a buffer that is too small. */
+uint32_t orc_dna_model(orc_dna* d, int family, uint64_t ctx, uint32_t* out, uint32_t cap)
+{
+	orc_ctxmap* ms[] = { &d->m_read_type, &d->m_rev_comp, &d->m_seen, &d->m_len_bits, &d->m_len_data, &d->m_symbols, &d->m_symbols_n,
+		&d->m_read_id, &d->m_read_id_short, &d->m_anchor_len, &d->m_skip_local, &d->m_skip_distant, &d->m_tuple_type };
+	if (family < 0 || family >= (int)(sizeof(ms) / sizeof(ms[0]))) return 0;
+	orc_ctxmap* c = ms[family];
+	if (cap < c->n_sym + 1) return 0;
+	size_t h = orc_ctxmap_find(c, ctx);
+	for (uint32_t i = 0; i < c->n_sym; ++i) out[i] = h == (size_t)-1 ? 1u : c->pool[h * c->n_sym + i];
+	out[c->n_sym] = h == (size_t)-1 ? c->n_sym : c->totals[h];
+	return c->n_sym;
 }
 
 /* Finish + GetOutput + Restart (entr_read.h:69-77) */

@@ -88,6 +88,8 @@ void orc_dna_add_ref(orc_dna*, const uint8_t* bases, uint32_t len);      /* CRef
 /* one read: its tuple stream in the App. A byte layout and the tuple count (es_t::size()) */
 void orc_dna_encode(orc_dna*, const uint8_t* es, size_t n_bytes, uint32_t n_tuples);
 size_t orc_dna_finish_part(orc_dna*, uint8_t* dst, size_t cap);
+/* test access: counters and total (out[n_sym]) of one model; family in the order of dna.hip's F_* enumeration; returns n_sym (0: bad family / cap) */
+uint32_t orc_dna_model(orc_dna*, int family, uint64_t ctx, uint32_t* out, uint32_t cap);
 
 /* ---- a8-a12: CEncoder (encoder.{h,cpp}, edit_script.h, libs/edlib, utils.h:700-1131) ---------------- */
 typedef struct orc_encoder orc_encoder;

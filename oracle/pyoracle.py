@@ -64,6 +64,8 @@ def lib():
         L.orc_dna_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32]
         L.orc_dna_finish_part.restype = C.c_size_t
         L.orc_dna_finish_part.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.orc_dna_model.restype = C.c_uint32
+        L.orc_dna_model.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint32]
         L.orc_encoder_new.restype = C.c_void_p
         L.orc_encoder_new.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32]
         L.orc_encoder_free.argtypes = [C.c_void_p]
@@ -206,6 +208,11 @@ class QualCoder:
         return out[:len(bases)]
 
 
+# the DNA coder's model families in the order both orc_dna_model and cl_dna_coder_model number them
+DNA_FAMILIES = ("read_type", "rev_comp", "seen", "len_bits", "len_data", "symbols", "symbols_n", "read_id", "read_id_short",
+                "anchor_len", "skip_local", "skip_distant", "tuple_type")
+
+
 class DnaCoder:
     """CDNACoder + the part framing of CEntrComprReads."""
     def __init__(self, max_alt_refs: int, level: int, start_read_id: int = 0):
@@ -229,6 +236,14 @@ class DnaCoder:
         buf = np.zeros(n, np.uint8)
         m = lib().orc_dna_finish_part(self.h, buf.ctypes.data, n)
         return buf[:m].tobytes()
+
+    def model(self, family: int, ctx: int) -> np.ndarray:
+        """Counters and, last, the total of one model (family: the index in DNA_FAMILIES); all ones for a context never coded."""
+        out = np.zeros(257, np.uint32)
+        n = lib().orc_dna_model(self.h, family, ctx, out.ctypes.data, len(out))
+        if not n:
+            raise ValueError(f"no DNA model family {family}")
+        return out[:n + 1].copy()
 
 
 class Encoder:

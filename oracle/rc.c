@@ -53,6 +53,14 @@ orc_model orc_ctxmap_get(orc_ctxmap* c, uint64_t ctx, uint32_t** total_slot)
 	return m;
 }
 
+/* index of the model of ctx, (size_t)-1 if the context was never used: a look that creates nothing */
+size_t orc_ctxmap_find(const orc_ctxmap* c, uint64_t ctx)
+{
+	size_t h = mix64(ctx) & (c->tsz - 1);
+	while (c->keys[h] != ~0ULL && c->keys[h] != ctx) h = (h + 1) & (c->tsz - 1);
+	return c->keys[h] == ~0ULL ? (size_t)-1 : c->vals[h];
+}
+
 /* CRangeCoderModel*::Encode / EncodeExcluding (rc.h:810-842, 880-925): cumulative and total skip the
  * excluded symbols; the update is the ordinary one. */
 void orc_encode_sym(orc_rce* e, orc_ctxmap* c, uint64_t ctx, uint32_t sym, int exc1, int exc2)

@@ -100,6 +100,7 @@ typedef struct {
 void orc_ctxmap_init(orc_ctxmap* c, uint32_t n_sym, uint32_t max_total, uint32_t adder);
 void orc_ctxmap_free(orc_ctxmap* c);
 orc_model orc_ctxmap_get(orc_ctxmap* c, uint64_t ctx, uint32_t** total_slot);   /* creates an all-ones model on first use */
+size_t orc_ctxmap_find(const orc_ctxmap* c, uint64_t ctx);                        /* model index, (size_t)-1 if never used */
 
 /* encode / decode one symbol in context ctx, optionally excluding up to two symbols (rc.h:810-842,880-925) */
 void orc_encode_sym(orc_rce* e, orc_ctxmap* c, uint64_t ctx, uint32_t sym, int exc1, int exc2);
