@@ -40,6 +40,22 @@ class Digest(C.Structure):
         return self.reads, self.symbols, self.sum
 
 
+class Report(C.Structure):
+    """cl_report: the content report; every field adds over disjoint sets of reads except len_min / len_max (min / max) and has_qual (or)."""
+    _fields_ = [("reads", C.c_uint64), ("bases", C.c_uint64), ("base_count", C.c_uint64 * 5), ("len_min", C.c_uint64), ("len_max", C.c_uint64),
+                ("len_hist", C.c_uint64 * 33), ("len_bases", C.c_uint64 * 33), ("has_qual", C.c_uint64), ("q_reads", C.c_uint64), ("q_symbols", C.c_uint64),
+                ("mean_q_hist", C.c_uint64 * 96), ("q_joint", (C.c_uint64 * 96) * 96)]
+
+    def as_dict(self):
+        """plain ints and numpy arrays, field by field"""
+        import numpy as np
+        out = {}
+        for name, t in self._fields_:
+            v = getattr(self, name)
+            out[name] = int(v) if t is C.c_uint64 else np.ctypeslib.as_array(v).copy()
+        return out
+
+
 _P = C.c_void_p
 class CompressParams(C.Structure):
     _fields_ = [("k", C.c_uint32), ("f", C.c_uint32), ("ci", C.c_uint32), ("cs", C.c_uint32), ("c", C.c_uint32),
@@ -88,6 +104,16 @@ _SIG = {
     "cl_qual_values": (C.c_int32, [_P, C.POINTER(QualParams), _P, _P, _P, _P, C.c_uint64]),
     "cl_qual_values_host": (C.c_int32, [C.POINTER(QualParams), _P, _P, C.c_uint64, _P]),
     "cl_digest_qual_values_host": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(Digest)]),
+    "cl_report_clear": (None, [C.POINTER(Report)]),
+    "cl_report_add": (None, [C.POINTER(Report), C.POINTER(Report)]),
+    "cl_report_bases": (C.c_int32, [_P, _P, C.POINTER(Report)]),
+    "cl_report_quals": (C.c_int32, [_P, C.POINTER(QualParams), _P, _P, _P, C.c_uint64, C.c_uint32, C.POINTER(Report)]),
+    "cl_report_bases_host": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(Report)]),
+    "cl_report_quals_host": (C.c_int32, [C.POINTER(QualParams), _P, _P, C.c_uint64, C.POINTER(Report)]),
+    "cl_report_values_host": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(Report)]),
+    "cl_ctx_set_report": (None, [_P, C.c_int]),
+    "cl_ctx_report": (C.c_int32, [_P, C.POINTER(Report)]),
+    "cl_compressor_report": (C.c_int32, [_P, C.POINTER(Report)]),
     "cl_digest_bases": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(Digest)]),
     "cl_digest_quals": (C.c_int32, [_P, C.POINTER(QualParams), _P, _P, _P, C.c_uint64, C.POINTER(Digest)]),
     "cl_digest_bases_host": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(Digest)]),

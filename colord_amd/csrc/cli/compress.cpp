@@ -201,6 +201,9 @@ int run_compress(int argc, char** argv)
 	if (O.digest) cl_ctx_set_digest(ctx, 1);
 	const bool digest_values = want_digest_values(O, with_qual);
 	if (digest_values) cl_ctx_set_digest_values(ctx, 1);
+	check_report_options(O, with_qual);
+	if (O.report) cl_ctx_set_report(ctx, 1);
+	std::vector<uint64_t> report_lens;                          // --report: every read length, as the reader hands the reads over in pass 1 (N50 / N90)
 	ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, nullptr, estimated_bases(R), &cmp), "cl_compressor_create");
 	if (O.qual_domain_symbols)
 	{
@@ -221,6 +224,7 @@ int run_compress(int argc, char** argv)
 		auto t0 = std::chrono::steady_clock::now();
 		auto lapse = [&](double& acc) { const auto t = std::chrono::steady_clock::now(); acc += std::chrono::duration<double>(t - t0).count(); t0 = t; };
 		DevChunk dc = DevChunk::from(host, with_qual);
+		if (O.report) for (size_t i = 0; i + 1 < host.off.size(); ++i) report_lens.push_back(host.off[i + 1] - host.off[i]);
 		lapse(t_check);
 		up.upload(ctx, host, dc);
 		lapse(t_upload);
@@ -326,6 +330,12 @@ int run_compress(int argc, char** argv)
 			if (dv.reads != n || dv.symbols != total) die("internal: the content digest did not see every read");
 		}
 		add_digest(ar, dd, with_qual && O.P.qual_mode != 8 ? &dq : nullptr, hdr.digest, digest_values ? &dv : nullptr);
+	}
+	if (O.report)
+	{
+		ReportSet S;
+		ck(ctx, cl_compressor_report(cmp, S.r.get()), "cl_compressor_report");
+		add_report(ar, S, report_lens, n, total, with_qual && O.P.qual_mode != 8);
 	}
 	if (O.qual_domain_symbols)
 	{

@@ -7,6 +7,7 @@
 #include "fastx_input.hpp"
 #include "genome_io.hpp"
 #include "digest_stream.hpp"
+#include "report_stream.hpp"
 #include <ctime>
 #include <mutex>
 
@@ -308,6 +309,23 @@ inline void add_digest(ArchiveWriter& ar, const cl_digest& dna, const cl_digest*
 	DigestSet S; S.flags = 1u | (qual ? 2u : 0u) | 4u | (qual && values ? 8u : 0u); S.d[0] = dna; if (qual) S.d[1] = *qual; S.d[2] = header; if (qual && values) S.d[3] = *values;
 	const std::vector<uint8_t> b = S.pack();
 	ar.add(ar.reg("hipdigest"), b.data(), b.size(), 0);
+}
+// --report: the `hipreport` stream (report_stream.hpp), before finish_archive: the additive part as the compressors' contexts counted it, N50 / N90
+// from the read lengths the reader saw; what was counted must be every read of the input
+inline void add_report(ArchiveWriter& ar, ReportSet& S, const std::vector<uint64_t>& lens, uint64_t n_reads, uint64_t n_bases, bool coded_quals)
+{
+	const cl_report& r = *S.r;
+	if (r.reads != n_reads || r.bases != n_bases || lens.size() != n_reads || (coded_quals && (r.q_reads != n_reads || r.q_symbols != n_bases)) || (!coded_quals && r.has_qual))
+		die("internal: the content report did not see every read");
+	S.n50 = rp_nxx(lens, 50); S.n90 = rp_nxx(lens, 90);
+	const std::vector<uint8_t> b = S.pack();
+	ar.add(ar.reg("hipreport"), b.data(), b.size(), 0);
+}
+// --report with a *-fix mode: the -D values must be qualities the report can index
+inline void check_report_options(const Options& O, bool with_qual)
+{
+	if (!O.report || !with_qual) return;
+	if (O.P.qual_mode >= 4 && O.P.qual_mode <= 6) for (uint32_t v : O.qd.rev) if (v > 95) die("--report: a -D value above 95 is no quality the report can count");
 }
 // `hipqdomains` (--qual-domain-symbols): u64 count, then per model domain of the quality stream its first `qual` part and its first read
 inline void add_qual_domains(ArchiveWriter& ar, const std::vector<uint64_t>& first_part, const std::vector<uint64_t>& part_first_read)

@@ -20,6 +20,7 @@ struct RankOut {
 	uint64_t n_reads = 0, mean_read_len = 0; uint32_t sparse_range = 0, n_refs = 0; cl_kmer_stats ks{};
 	uint64_t dna_base = 0, qual_base = 0, qual_framed = 0;     // where its framed `dna` / `qual` parts start in the file; bytes of the latter
 	uint64_t moved = 0;
+	std::unique_ptr<cl_report> report;                         // --report: what this rank's compressor counted of its reads
 	cl_digest dig[3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } }, dig_all[3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } };      // --digest: dna / qual / (--digest-values) qual-values of this rank's reads; of all ranks (as gathered with the byte counts)
 };
 uint32_t varint_len(uint64_t x) { uint32_t n = 1; for (; x; x >>= 8) ++n; return n; }
@@ -80,6 +81,7 @@ int run_compress_multi(const Options& O)
 	}
 	HeaderCoder hdr; hdr.want_digest = O.digest; hdr.start(R, (uint32_t)n, O.header_mode);
 	const bool digest_values = want_digest_values(O, with_qual);
+	check_report_options(O, with_qual);
 
 	// transports
 	std::vector<std::unique_ptr<Transport>> tp(world);
@@ -116,6 +118,7 @@ int run_compress_multi(const Options& O)
 		const bool digest_qual = with_qual && O.P.qual_mode != 8;
 		if (O.digest && !independent) cl_ctx_set_digest(ctx, 1);
 		if (digest_values && !independent) cl_ctx_set_digest_values(ctx, 1);
+		if (O.report) cl_ctx_set_report(ctx, 1);                            // (the report has no read indices: a rank's and an independent domain's compressor count alike)
 		ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, T ? &X : nullptr, my_bases, &cmp), "cl_compressor_create");
 		if (GM.on) GM.count_kmers(ctx, cmp);
 		// chunks of whole reader packs (the packs are cut from this rank's first read on: in_reads.cpp:62-77).  The chunk size follows the
@@ -201,6 +204,7 @@ int run_compress_multi(const Options& O)
 		// where this rank's parts go: an all-gather of the framed byte counts, an exclusive sum, pwrite — `dna` of all ranks first, then `qual`
 		if (O.digest && !independent) ck(ctx, cl_compressor_digest(cmp, &RO.dig[0], &RO.dig[1]), "cl_compressor_digest");
 		if (digest_values && !independent) ck(ctx, cl_compressor_digest_values(cmp, &RO.dig[2]), "cl_compressor_digest_values");
+		if (O.report) { RO.report.reset(new cl_report); ck(ctx, cl_compressor_report(cmp, RO.report.get()), "cl_compressor_report"); }
 		// framed bytes of `dna`, `qual`; the content digests travel with them (--digest-values: the fourth triple too, 11 values instead of 8)
 		uint64_t mine[11] = { 0, 0, RO.dig[0].reads, RO.dig[0].symbols, RO.dig[0].sum, RO.dig[1].reads, RO.dig[1].symbols, RO.dig[1].sum, RO.dig[2].reads, RO.dig[2].symbols, RO.dig[2].sum };
 		const uint32_t n_mine = digest_values ? 11 : 8; const int n_dig = digest_values ? 3 : 2;
@@ -287,6 +291,13 @@ int run_compress_multi(const Options& O)
 		if (dd[0].reads != n || dd[0].symbols != total) die("internal: the content digest did not see every read");
 		if (digest_values && (dd[2].reads != n || dd[2].symbols != total)) die("internal: the content digest did not see every read");
 		add_digest(ar, dd[0], with_qual && O.P.qual_mode != 8 ? &dd[1] : nullptr, hdr.digest, digest_values ? &dd[2] : nullptr);
+	}
+	if (O.report)
+	{	// the ranks' (domains') reports added — they are threads of this process, nothing travels — and the lengths of the one reader for N50 / N90
+		ReportSet rep;
+		for (uint32_t r = 0; r < world; ++r) if (out[r].report) rp_add(rep.r.get(), out[r].report.get());
+		std::vector<uint64_t> lens(n); for (uint64_t i = 0; i < n; ++i) lens[i] = S.len(i);
+		add_report(ar, rep, lens, n, total, with_qual && O.P.qual_mode != 8);
 	}
 	finish_archive(ar, O, R, tot);
 	if (use_rccl) rccl.destroy_all();

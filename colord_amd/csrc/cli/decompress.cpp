@@ -107,9 +107,21 @@ struct DeviceQualDecoder {
 
 int run_info(int argc, char** argv)
 {
-	if (argc < 3) { fprintf(stderr, "usage: colord_hip info archive.colord\n"); return 1; }
+	bool want_report = false, json = false; std::vector<std::string> pos;
+	for (int i = 2; i < argc; ++i) { const std::string a = argv[i]; if (a == "--report") want_report = true; else if (a == "--json") json = true; else pos.push_back(a); }
+	if (pos.size() != 1 || (json && !want_report)) { fprintf(stderr, "usage: colord_hip info [--report [--json]] archive.colord\n"); return 1; }
+	const std::string& path = pos[0];
 	ArchiveReader ar;
-	if (!ar.open(argv[2])) die(std::string("cannot open archive: ") + argv[2]);
+	if (!ar.open(path)) die("cannot open archive: " + path);
+	if (want_report)
+	{	// the stored content report alone, on stdout: nothing is decoded
+		ar.close();
+		ReportSet S; const int have = read_hipreport(path, S);
+		if (have == 0) die("no content report is stored in this archive (written without --report); `colord_hip check` prints what it decodes to");
+		if (have < 0) die("the archive's `hipreport` stream is not one this build reads");
+		if (json) print_report_json(stdout, S); else print_report(stdout, S, false);
+		return 0;
+	}
 	std::vector<uint8_t> b; uint64_t meta = 0;
 	if (!ar.part(ar.id("info"), 0, b, meta) || b.size() < 40) die("archive without a readable `info` stream");
 	ArchiveInfo I;
@@ -119,7 +131,12 @@ int run_info(int argc, char** argv)
 		I.version_major, I.version_minor, I.version_patch, (unsigned long long)I.total_bytes, (unsigned long long)I.total_bases, I.total_reads, asctime(localtime(&t)), I.command_line.c_str());
 	ar.close();
 	DigestSet stored;                                                          // archives written with --digest: the content digests they must decode to
-	if (read_hipdigest(argv[2], stored) > 0) for (int j = 0; j < 4; ++j) if (const int i = DigestSet::in_order(j); (stored.flags >> i) & 1) fprintf(stderr, "content digest: %s\n", stored.line(i).c_str());
+	if (read_hipdigest(path, stored) > 0) for (int j = 0; j < 4; ++j) if (const int i = DigestSet::in_order(j); (stored.flags >> i) & 1) fprintf(stderr, "content digest: %s\n", stored.line(i).c_str());
+	ReportSet rep;
+	if (const int have = read_hipreport(path, rep); have > 0)
+		fprintf(stderr, "content report: %llu reads, %llu bases, N50 %llu, %s (`colord_hip info --report [--json]` prints it)\n", (unsigned long long)rep.r->reads, (unsigned long long)rep.r->bases, (unsigned long long)rep.n50,
+			rep.r->has_qual ? "input against stored quality values" : "no quality part");
+	else if (have < 0) fprintf(stderr, "content report: a `hipreport` stream this build cannot read\n");
 	return 0;
 }
 
@@ -140,7 +157,7 @@ static void format_record(std::vector<char>& line, const Record& r, bool is_fast
 	}
 }
 // what decoding an archive gave: its records, and (asked for) the content digests of what the decoders returned
-struct Decoded { uint64_t n_rec = 0; DigestSet computed; size_t domains = 0, at_a_time = 0; };
+struct Decoded { uint64_t n_rec = 0; DigestSet computed; size_t domains = 0, at_a_time = 0; bool want_report = false; ReportSet report; std::vector<uint64_t> lens; };
 
 // Archives with INDEPENDENT model domains (`colord_hip compress-* --domains K`): every domain is decoded by a worker of its own — three
 // stream threads each, as for a whole archive — into a file of its own next to the output; the files are then joined in order.  The ids
@@ -168,6 +185,7 @@ static bool decode_domains(const std::string& arc, const std::string& genome, co
 				RecordStream r(arc, genome, (int)d, &hc);
 				if (want_digest) r.enable_digest();
 				if (want_values) r.enable_digest_values();
+				if (D.want_report) r.enable_report();
 				r.prefetch();
 				{ static std::mutex hm; std::lock_guard<std::mutex> l(hm); if (ht.joinable()) ht.join(); }
 				if (!hc.err.empty()) throw std::runtime_error("header stream: " + hc.err);
@@ -180,6 +198,7 @@ static bool decode_domains(const std::string& arc, const std::string& genome, co
 				if (out && fclose(out) != 0) ok = false;
 				if (!ok) throw std::runtime_error("cannot write " + tmp[d] + " (disk full?)");
 				if (want_digest) dig[d] = r.digests();
+				if (D.want_report) { std::lock_guard<std::mutex> l(mu); r.report_into(D.report, D.lens); }
 			}
 			catch (const std::exception& e) { errs[d] = e.what(); }
 		}
@@ -224,6 +243,7 @@ static void decode_archive(const std::string& arc, const std::string& genome, co
 		RecordStream rs(arc, genome);
 		if (want_digest) rs.enable_digest();
 		if (want_values) rs.enable_digest_values();
+		if (D.want_report) rs.enable_report();
 		if (gpu >= 0)
 		{
 			if (rs.n_qual_domains())
@@ -252,6 +272,7 @@ static void decode_archive(const std::string& arc, const std::string& genome, co
 		if (out && (fflush(out) != 0 || ferror(out))) write_ok = false;
 		if (out && fclose(out) != 0) write_ok = false;
 		if (want_digest && write_ok) D.computed = rs.digests();
+		if (D.want_report && write_ok) rs.report_into(D.report, D.lens);
 		dev.report();
 	}
 	catch (const std::exception& e) { fail(e.what()); }
@@ -276,14 +297,24 @@ int run_decompress(int argc, char** argv)
 	// an archive written with --digest is checked while it is decoded: the stream threads digest what they decode
 	DigestSet stored; const int have = ignore_digest ? 0 : read_hipdigest(pos[0], stored);
 	if (have < 0) die("the archive's `hipdigest` stream is not one this build reads (--ignore-digest decodes without the check)");
-	Decoded D;
+	// ... and one written with --report likewise: the output side of the stored content report against what is decoded
+	ReportSet stored_rep; const int have_rep = ignore_digest ? 0 : read_hipreport(pos[0], stored_rep);
+	if (have_rep < 0) die("the archive's `hipreport` stream is not one this build reads (--ignore-digest decodes without the check)");
+	Decoded D; D.want_report = have_rep > 0;
 	// (the qual-values digest only where the archive stores one: --digest-values)
-	decode_archive(pos[0], genome, pos[1], dom_threads, have > 0, have > 0 && ((stored.flags >> 3) & 1), have > 0, gpu, D);
+	decode_archive(pos[0], genome, pos[1], dom_threads, have > 0, have > 0 && ((stored.flags >> 3) & 1), have > 0 || have_rep > 0, gpu, D);
 	if (have > 0)
 	{
 		const std::string bad = digest_mismatch(stored, D.computed);
 		if (!bad.empty()) { (void)remove(pos[1].c_str()); die("content digest mismatch, the archive does not hold what was compressed: " + bad + " (no output was written; --ignore-digest decodes regardless)"); }
 		fprintf(stderr, "content digest: ok (%s)\n", stored.names().c_str());
+	}
+	if (have_rep > 0)
+	{
+		D.report.n50 = rp_nxx(D.lens, 50); D.report.n90 = rp_nxx(D.lens, 90);
+		const std::string bad = report_mismatch(stored_rep, D.report);
+		if (!bad.empty()) { (void)remove(pos[1].c_str()); die("content report mismatch, the archive does not hold what was compressed: " + bad + " (no output was written; --ignore-digest decodes regardless)"); }
+		fprintf(stderr, "content report: ok\n");
 	}
 	if (D.domains) fprintf(stderr, "colord_hip: %llu records decompressed (%zu independent domains, %zu at a time)\n", (unsigned long long)D.n_rec, D.domains, D.at_a_time);
 	else fprintf(stderr, "colord_hip: %llu records decompressed\n", (unsigned long long)D.n_rec);
@@ -306,15 +337,27 @@ int run_check(int argc, char** argv)
 	}
 	if (pos.size() != 1) { fprintf(stderr, "usage: colord_hip check [-G reference_genome.fa] [--gpu N] archive.colord\n"); return 1; }
 	DigestSet stored; const int have = read_hipdigest(pos[0], stored);
-	Decoded D;
+	ReportSet stored_rep; const int have_rep = read_hipreport(pos[0], stored_rep);
+	Decoded D; D.want_report = true;
 	decode_archive(pos[0], genome, "", dom_threads, true, true, false, gpu, D);
+	D.report.n50 = rp_nxx(D.lens, 50); D.report.n90 = rp_nxx(D.lens, 90);
+	// the content report: without a stored one the output side of what was decoded is printed; with one the two are compared
+	int rep_status = 0;
+	auto check_report = [&]() {
+		if (have_rep == 0) { printf("decoded content (no content report is stored in this archive; written without --report):\n"); print_report(stdout, D.report, true); return; }
+		if (have_rep < 0) { printf("the archive's `hipreport` stream is not one this build reads\n"); rep_status = 1; return; }
+		const std::string bad = report_mismatch(stored_rep, D.report);
+		if (!bad.empty()) { printf("content report mismatch: %s\n", bad.c_str()); rep_status = 1; return; }
+		printf("content report: ok\n");
+	};
 	for (int i = 0; i < 3; ++i) printf("%s\n", D.computed.line(i).c_str());
 	if ((D.computed.flags >> 3) & 1) printf("%s\n", D.computed.line(3).c_str());      // (any archive with a coded quality stream, the reference's included)
-	if (have == 0) { printf("no content digest is stored in this archive (written without --digest); %llu records decode\n", (unsigned long long)D.n_rec); return 0; }
+	check_report();
+	if (have == 0) { printf("no content digest is stored in this archive (written without --digest); %llu records decode\n", (unsigned long long)D.n_rec); return rep_status; }
 	if (have < 0) { printf("the archive's `hipdigest` stream is not one this build reads\n"); return 1; }
 	for (int j = 0; j < 4; ++j) if (const int i = DigestSet::in_order(j); (stored.flags >> i) & 1) printf("stored %s\n", stored.line(i).c_str());
 	const std::string bad = digest_mismatch(stored, D.computed);
 	if (!bad.empty()) { printf("content digest mismatch: %s\n", bad.c_str()); return 1; }
 	printf("content digest: ok (%s)\n", stored.names().c_str());
-	return 0;
+	return rep_status;
 }

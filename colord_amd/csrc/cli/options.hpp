@@ -39,6 +39,7 @@ struct Options {
 	bool verify_streams = false;                    // --verify-streams: cl_ctx_set_verify_streams on every compressor's context
 	bool digest = false;                            // --digest: content digests of the input (cl_ctx_set_digest; ids on the host) in a `hipdigest` stream
 	bool digest_values = false;                     // --digest-values: --digest and the qual-values digest (cl_ctx_set_digest_values); `hipdigest` version 2
+	bool report = false;                            // --report: the content report of the input (cl_ctx_set_report) in a `hipreport` stream
 	uint64_t qual_domain_symbols = 0;               // --qual-domain-symbols N: the quality models start afresh about every N symbols (cl_compressor_set_qual_domain_symbols; stream `hipqdomains`)
 	int gpus = 1; std::vector<int> gpu_list; std::string transport = "rccl";   // --gpus N [--gpu-list a,b,..] [--transport rccl|host]: reads sharded over N GPUs (run_compress_multi)
 	Preset P{}; QDef qd;                            // resolved by parse_options: the preset of source and priority with the options laid over it, the quality thresholds / representatives
@@ -49,7 +50,7 @@ inline void usage()
 {
 	fprintf(stderr,
 		"usage: colord_hip compress-ont|compress-pbhifi|compress-pbraw [options] input.fastq|fasta[.gz] output.colord\n"
-		"       colord_hip decompress [--ignore-digest] [--gpu N] archive.colord output.fastq\n       colord_hip check [--gpu N] archive.colord\n       colord_hip info archive.colord\n"
+		"       colord_hip decompress [--ignore-digest] [--gpu N] archive.colord output.fastq\n       colord_hip check [--gpu N] archive.colord\n       colord_hip info [--report [--json]] archive.colord\n"
 		"options (as the reference, arg_parse.cpp:455-640):\n"
 		"  -p,--priority ratio|balanced|memory   -k,--kmer-len K with -a,--anchor-len A (both or none)\n"
 		"  -q,--qual org|none|avg|2-fix|4-fix|5-fix|2-avg|4-avg|5-avg   -T,--qual-thresholds a,b,..   -D,--qual-values a,b,..\n"
@@ -77,6 +78,16 @@ inline void usage()
 		"                     version 2, 104 bytes).  `colord_hip decompress` / `check` digest the quality bytes as they are handed to the writer, whichever decoder made them (host, or\n"
 		"                     --gpu): the hole --digest leaves between the decoded symbols and the quality line is closed.  With -q none or FASTA input there are no values: as --digest.\n"
 		"                     Cost: one more pass over the quality bytes per chunk, two in the *-avg modes (not measured on a GPU yet)\n"
+		"  --report           a content report of the input, counted on the device before any kernel of the compressor touches it, is stored in the archive (stream `hipreport`; the\n"
+		"                     reference's decompressor ignores it): reads, bases, base composition (A C G T N), read lengths (min, max, histogram by bit length, N50, N90) and, with a\n"
+		"                     coded quality stream, the exact joint distribution of INPUT quality against the quality VALUE the archive decodes to (the quantity of --digest-values), and\n"
+		"                     the reads' mean qualities — the arithmetic mean of the Phred values per read, NOT the error-probability mean other tools print.  `colord_hip info --report\n"
+		"                     [--json]` prints it without decoding anything, with the share of bases unchanged, MAE, RMSE and max |delta| of the quality mode.  `colord_hip decompress` /\n"
+		"                     `check` recompute the output side (reads, bases, composition, lengths, N50, N90, the stored values' distribution) from what they decode: a difference names\n"
+		"                     the first differing field with both numbers, no output file and exit 1 (--ignore-digest decodes regardless).  The INPUT side cannot be recomputed from a lossy\n"
+		"                     archive and is not checked.  Same report with any --part-symbols, --stream-input, -G [-s], --domains, --gpus: all of them read the input through one reader in\n"
+		"                     one process, which has every read length for N50 / N90.  A *-fix mode needs -D values <= 95.  With -q none or FASTA input there is no quality part.\n"
+		"                     Cost: one pass over 0.375 bytes per base and one over the quality bytes per chunk, two in the *-avg modes (not measured on a GPU yet)\n"
 		"  --qual-domain-symbols N   model domains of the QUALITY stream alone: its adaptive models start afresh at the first part boundary at which a domain holds N coded\n"
 		"                     symbols, and the starts are recorded (stream `hipqdomains`).  `colord_hip decompress --gpu N` / `check --gpu N` then decode the domains side by\n"
 		"                     side on the device, one lane each; without --gpu they decode on the host as one chain that starts afresh at every domain.  The k-mer set, the\n"
@@ -142,6 +153,7 @@ inline Options parse_options(int argc, char** argv)
 		else if (a == "--verify-streams") O.verify_streams = true;
 		else if (a == "--digest") O.digest = true;
 		else if (a == "--digest-values") O.digest = O.digest_values = true;
+		else if (a == "--report") O.report = true;
 		else if (a == "--parse-threads") { O.parse_threads = atoi(need(i).c_str()); if (O.parse_threads < 1 || O.parse_threads > 256) die("--parse-threads must be in [1, 256]"); }
 		else if (a == "-h" || a == "--help") { usage(); exit(0); }
 		else if (!a.empty() && a[0] == '-' && a.size() > 1) die("unknown option " + a);

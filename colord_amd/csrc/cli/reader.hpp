@@ -14,6 +14,7 @@
 #include "archive.hpp"
 #include "genome_io.hpp"
 #include "digest_stream.hpp"
+#include "report_stream.hpp"
 #include <condition_variable>
 #include <deque>
 #include <functional>
@@ -177,6 +178,9 @@ class RecordStream {
 	bool want_digest = false; cl_digest dig_dna{ 0, 0, 0 }, dig_qual{ 0, 0, 0 }, dig_hdr{ 0, 0, 0 };
 	// qual-values: the quality thread digests the quality BYTES of every part as it hands them on to the writer — whichever decoder made them
 	bool want_values = false; cl_digest dig_qval{ 0, 0, 0 };
+	// content report (report_stream.hpp): the DNA thread counts the bases and lengths of every part it decodes, the quality thread the quality
+	// bytes where they are handed on to the writer (the place of the qual-values digest); each thread has a report of its own
+	bool want_report = false; ReportSet rep_dna, rep_qual; std::vector<uint64_t> rep_lens;
 	uint64_t first_read_index() const { return only_domain >= 0 ? dom_read[only_domain] : 0; }
 	size_t part_begin() const { return only_domain >= 0 ? (size_t)dom_part[only_domain] : 0; }
 	size_t part_end() const { return only_domain >= 0 && (size_t)only_domain + 1 < dom_part.size() ? (size_t)dom_part[only_domain + 1] : ar.n_parts(s_dna); }
@@ -201,6 +205,15 @@ public:
 	void enable_digest() { if (!started) want_digest = true; }
 	// with enable_digest: also the qual-values digest (flag off without a coded quality stream, as for qual)
 	void enable_digest_values() { if (!started) want_values = true; }
+	// before the first record is asked for: the output side of the content report is counted from what is decoded.  report_into(): after
+	// next() has returned false — adds it to S and the read lengths (for N50 / N90, which do not add) to lens
+	void enable_report() { if (!started) want_report = true; }
+	void report_into(ReportSet& S, std::vector<uint64_t>& lens) const
+	{
+		rp_add(S.r.get(), rep_dna.r.get());
+		if (fastq && M.qual_mode != 8) rp_add(S.r.get(), rep_qual.r.get());
+		lens.insert(lens.end(), rep_lens.begin(), rep_lens.end());
+	}
 	DigestSet digests() const
 	{
 		DigestSet s; s.flags = 1u | (fastq && M.qual_mode != 8 ? 2u : 0u) | (ext_hdr ? 0u : 4u) | (want_values && fastq && M.qual_mode != 8 ? 8u : 0u);
@@ -332,6 +345,7 @@ inline void RecordStream::start()
 			if (s != CL_OK) { err_dna = cl_dna_decoder_error(d); break; }
 			x.bases.resize(got);
 			if (want_digest) { if (!dg_bases_host(x.bases.data(), x.off.data(), n_reads, g, &dig_dna)) { err_dna = "more reads than the content digest can index"; break; } g += n_reads; }
+			if (want_report) { (void)rp_bases_host(x.bases.data(), x.off.data(), n_reads, rep_dna.r.get()); for (uint64_t i = 0; i < n_reads; ++i) rep_lens.push_back(x.off[i + 1] - x.off[i]); }
 			if (fastq) { ReadPart cp; cp.bases = x.bases; cp.off = x.off; const uint64_t w = cp.bases.size(); q_bases_for_qual.push(std::move(cp), w); }
 			q_reads.push(std::move(x));
 		}
@@ -351,7 +365,9 @@ inline void RecordStream::start()
 		// the ONE place where decoded qualities leave for the writer, behind the host decoder and behind the batches of the device decoder:
 		// `first` = the part's first read in the whole input
 		const bool values = want_digest && want_values && M.qual_mode != 8;
+		const bool report = want_report && M.qual_mode != 8;
 		auto hand_on = [&](ReadPart& y, uint64_t first) {
+			if (report) (void)rp_values_host(y.quals.data(), y.off.data(), y.off.size() - 1, rep_qual.r.get());
 			if (values && !dg_qual_ascii_host(y.quals.data(), y.off.data(), y.off.size() - 1, first, &dig_qval)) throw std::runtime_error("more reads than the content digest can index");
 			y.bases.clear(); y.bases.shrink_to_fit();
 			q_quals.push(std::move(y));

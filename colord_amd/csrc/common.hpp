@@ -350,6 +350,8 @@ struct cl_ctx {
 	cl_digest digest_dna{ 0, 0, 0 }, digest_qual{ 0, 0, 0 };   // the totals so far (owner thread only)
 	bool digest_values = false;                  // cl_ctx_set_digest_values: the same calls digest the quality VALUES of their input (k_qual_values)
 	cl_digest digest_qval{ 0, 0, 0 };
+	bool report = false;                         // cl_ctx_set_report: the same calls add the content report of their input (report.hip)
+	cl_report* report_acc = nullptr;             // the total so far (owner thread only); made when the flag is first switched on, freed with the context
 	uint64_t gap_paths[11] = { 0 };              // cl_ctx_gap_paths: the last cl_encode_reads' gaps per size class 0..7, quad -> wave, giant -> wave, wave-pool redo rounds (owner thread only)
 	std::map<std::string, KernelTime> times;     // per-kernel accumulated HIP-event time of the last API call
 	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;

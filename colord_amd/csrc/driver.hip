@@ -18,6 +18,7 @@ extern "C" cl_status cl_compress_shard(cl_ctx* ctx, const cl_compress_params* P,
 	if (!n) return CL_OK;
 	if (ctx->digest) CL_TRY(digest_chunk(ctx, reads, cl_qual_coder_params(qual), d_quals, d_base_off, 0));     // from the input, before anything is made of it
 	if (ctx->digest_values) CL_TRY(digest_values_chunk(ctx, reads, cl_qual_coder_params(qual), d_quals, d_base_off, 0));
+	if (ctx->report) CL_TRY(report_chunk(ctx, reads, cl_qual_coder_params(qual), d_quals, d_base_off));
 	// the quality stream beside the whole DNA path where it may be (level 1, a context of its own)
 	ChunkCoder coder(ctx, P->level, dna, qual, ChunkIO{ reads, d_quals, d_base_off, h_part_bounds, n_parts, d_dna_out, dna_cap, h_dna_part_sizes, d_qual_out, qual_cap, h_qual_part_sizes, info });
 	coder.start_quality();

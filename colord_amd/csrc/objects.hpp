@@ -62,6 +62,8 @@ cl_status cl_es_verify_at(cl_ctx* ctx, const cl_reads* reads, const cl_reads* re
 cl_status digest_chunk(cl_ctx* ctx, const cl_reads* reads, const cl_qual_params* qparams, const uint8_t* d_quals, const uint64_t* d_base_off, uint64_t first_read);
 // (cl_ctx_set_digest_values): the qual-values digest of the same chunk, from the input quality bytes alone (nothing with qparams null or mode none)
 cl_status digest_values_chunk(cl_ctx* ctx, const cl_reads* reads, const cl_qual_params* qparams, const uint8_t* d_quals, const uint64_t* d_base_off, uint64_t first_read);
+// report.hip (cl_ctx_set_report): the content report of the same chunk — the arena and, with qparams, the input quality bytes — added to the context's total
+cl_status report_chunk(cl_ctx* ctx, const cl_reads* reads, const cl_qual_params* qparams, const uint8_t* d_quals, const uint64_t* d_base_off);
 const cl_qual_params* cl_qual_coder_params(const cl_qual_coder* q);     // qual.hip: the parameters the coder was created with
 
 // the DNA coder's state-independent half ahead of time (dna.hip): lookahead.hip walks the NEXT chunk's tuples from the hook that

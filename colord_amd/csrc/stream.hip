@@ -387,6 +387,7 @@ extern "C" cl_status cl_compressor_encode(cl_compressor* c, const cl_reads* read
 		uint64_t g = c->first_read; for (size_t i = 0; i < idx; ++i) g += c->chunk_reads[i];
 		CL_TRY(digest_values_chunk(ctx, reads, &c->Q, d_quals, d_base_off, g));
 	}
+	if (ctx->report) CL_TRY(report_chunk(ctx, reads, c->has_qual ? &c->Q : nullptr, d_quals, d_base_off));   // the content report of the chunk, from the same input
 	struct HooksOff { cl_compressor* c; ~HooksOff() { cl_dna_set_before_tail(c->dna, nullptr); cl_qual_set_before_tail(c->qual, nullptr); } } hooks_off{ c };
 	ChunkCoder coder(ctx, c->P.level, c->dna, c->qual, ChunkIO{ reads, d_quals, d_base_off, h_part_bounds, n_parts, d_dna_out, dna_cap, h_dna_part_sizes, d_qual_out, qual_cap, h_qual_part_sizes, info });
 	lookahead_quality(c, job.get(), coder);
@@ -434,6 +435,10 @@ extern "C" cl_status cl_compressor_digest(const cl_compressor* c, cl_digest* dna
 extern "C" cl_status cl_compressor_digest_values(const cl_compressor* c, cl_digest* out)
 {
 	return c ? cl_ctx_digest_values(c->ctx, out) : CL_E_INVALID;
+}
+extern "C" cl_status cl_compressor_report(const cl_compressor* c, cl_report* out)
+{
+	return c ? cl_ctx_report(c->ctx, out) : CL_E_INVALID;
 }
 
 // every context that codes for the compressor: its own (the DNA stream; the quality stream of levels 2 and 3) and the quality coder's

@@ -54,7 +54,8 @@ class _OrderedLib:
                   "cl_compressor_verified", "cl_ctx_set_verify_streams", "cl_ctx_verified_streams", "cl_compressor_verified_streams",
                   "cl_ctx_set_digest", "cl_ctx_digest", "cl_compressor_digest", "cl_digest_bases_host", "cl_digest_bytes_host", "cl_qual_decoder_set_digest", "cl_qual_decoder_digest",
                   "cl_ctx_set_digest_values", "cl_ctx_digest_values", "cl_compressor_digest_values", "cl_qual_values_host", "cl_digest_qual_values_host",
-                  "cl_qual_coder_domains", "cl_compressor_qual_domains", "cl_ctx_gap_paths")
+                  "cl_qual_coder_domains", "cl_compressor_qual_domains", "cl_ctx_gap_paths",
+                  "cl_report_clear", "cl_report_add", "cl_report_bases_host", "cl_report_quals_host", "cl_report_values_host", "cl_ctx_set_report", "cl_ctx_report", "cl_compressor_report")
 
     def __init__(self, lib, device):
         self._lib, self._device, self._cache = lib, device, {}
@@ -180,6 +181,38 @@ class Context:
         d = N.Digest()
         _check(None, self.lib.cl_ctx_digest_values(self.h, C.byref(d)))
         return d.triple()
+
+    def set_report(self, on: bool = True):
+        """cl_ctx_set_report: compress_shard() and compressors of this context add the content report of their input (cleared when switched on)."""
+        self.lib.cl_ctx_set_report(self.h, int(bool(on)))
+
+    def report(self) -> "N.Report":
+        """cl_ctx_report: the report so far on this context."""
+        r = N.Report()
+        _check(None, self.lib.cl_ctx_report(self.h, C.byref(r)))
+        return r
+
+    @staticmethod
+    def new_report() -> "N.Report":
+        r = N.Report()
+        N.load().cl_report_clear(C.byref(r))
+        return r
+
+    def report_bases(self, reads: "Reads", acc: "N.Report | None" = None) -> "N.Report":
+        """cl_report_bases: reads, bases, base composition and read lengths of an arena, added to acc."""
+        acc = self.new_report() if acc is None else acc
+        _check(self, self.lib.cl_report_bases(self.h, reads.h, C.byref(acc)))
+        return acc
+
+    def report_quals(self, reads: "Reads", quals: torch.Tensor, qual_off: torch.Tensor, mode: int, fwd=(), rev=(), flush_bytes: int = 0, max_blocks: int = 0,
+                     acc: "N.Report | None" = None) -> "N.Report":
+        """cl_report_quals: input quality against the value a decoder of `mode` (thresholds fwd, -D values rev) will write, and the reads' mean
+        qualities, added to acc.  flush_bytes / max_blocks (0: the defaults) change no result."""
+        prm = self._qual_params(mode, fwd, rev)
+        acc = self.new_report() if acc is None else acc
+        quals, qual_off = quals.contiguous(), qual_off.contiguous()
+        _check(self, self.lib.cl_report_quals(self.h, C.byref(prm), reads.h, quals.data_ptr() if quals.numel() else None, qual_off.data_ptr(), flush_bytes, max_blocks, C.byref(acc)))
+        return acc
 
     @staticmethod
     def _qual_params(mode, fwd, rev):
@@ -732,6 +765,12 @@ class Compressor(_Obj):
         d, q = N.Digest(), N.Digest()
         _check(None, self.ctx.lib.cl_compressor_digest(self.h, C.byref(d), C.byref(q)))
         return d.triple(), q.triple()
+
+    def report(self) -> "N.Report":
+        """cl_compressor_report: the content report of the chunks encoded so far (Context.set_report)."""
+        r = N.Report()
+        _check(None, self.ctx.lib.cl_compressor_report(self.h, C.byref(r)))
+        return r
 
     def digest_values(self):
         """cl_compressor_digest_values: (reads, symbols, sum) of the qual-values digest of the chunks encoded so far (Context.set_digest_values)."""

@@ -362,6 +362,44 @@ cl_status cl_qual_values(cl_ctx* ctx, const cl_qual_params* qparams, const cl_re
 cl_status cl_qual_values_host(const cl_qual_params* qparams, const uint8_t* h_quals, const uint64_t* h_off, uint64_t n, uint8_t* h_values);
 cl_status cl_digest_qual_values_host(const uint8_t* h_ascii_quals, const uint64_t* h_off, uint64_t n, uint64_t first_read, cl_digest* acc);
 
+/* ---- content report (no counterpart in the reference) — what the input holds and what the quality mode changes ------ */
+/* Every counter is unsigned 64-bit and adds over disjoint sets of reads, in any order; len_min / len_max combine by min / max
+ * (len_min is UINT64_MAX while reads == 0) and has_qual by or.  base_count: A, C, G, T, N (N = every position of a read whose bit is
+ * set in the arena's invalid mask; pad positions are no content).  len_hist / len_bases: reads, and their bases, by bit length of the
+ * read length (length 0 in bin 0).  The quality part (all zero and has_qual 0 for FASTA input and mode none): mean_q_hist per read of
+ * length > 0 floor(sum q / len) of the INPUT qualities, q = byte - 33, outside 0..95 counted as 0 — the arithmetic mean of the Phred
+ * values, not the error-probability mean; q_joint[in][out] = bases whose input quality is `in` and whose decoded quality value (the
+ * byte the decoder WRITES minus 33: the quantity of the qual-values digest) is `out`. */
+typedef struct cl_report {
+	uint64_t reads, bases, base_count[5], len_min, len_max, len_hist[33], len_bases[33];
+	uint64_t has_qual, q_reads, q_symbols, mean_q_hist[96], q_joint[96][96];
+} cl_report;
+void cl_report_clear(cl_report* r);
+void cl_report_add(cl_report* dst, const cl_report* src);
+/* On the device, added to *acc (host).  cl_report_bases: the content part of the arena, a wave per read, popcounts on the packed
+ * words and the invalid mask.  cl_report_quals: the quality part, persistent blocks of four waves that count every byte into a
+ * 96 x 96 matrix of 32-bit cells in LDS and add its non-zero cells to the 64-bit total at their end and whenever flush_bytes bytes
+ * or more were counted since the last time (0: the default, 2^30; clamped to 1 .. 2^32 - 2^16); max_blocks: the grid's bound (0: the
+ * default, four per CU).  Both arguments change no result.  d_quals / d_qual_off as for cl_qual_encode; nothing outside
+ * [d_qual_off[r], d_qual_off[r + 1]) is read for read r.  Mode none: nothing is added.  CL_E_INVALID before any launch: thresholds
+ * that do not fit the mode, a *-fix mode without a -D value for every bin or with one above 95.  CL_E_UNSUPPORTED: four consecutive
+ * reads of 2^32 or more quality bytes together (a 32-bit cell could wrap). */
+cl_status cl_report_bases(cl_ctx* ctx, const cl_reads* reads, cl_report* acc);
+cl_status cl_report_quals(cl_ctx* ctx, const cl_qual_params* qparams, const cl_reads* reads, const uint8_t* d_quals, const uint64_t* d_qual_off,
+                          uint64_t flush_bytes, uint32_t max_blocks, cl_report* acc);
+/* On the HOST.  cl_report_bases_host: codes as cl_dna_decode_part writes them.  cl_report_quals_host: from INPUT quality bytes, as
+ * the device.  cl_report_values_host: from DECODED quality lines (ASCII) — q_reads, q_symbols and the OUT marginal alone: every base
+ * is counted in q_joint[0][out], so only the column sums of such a report mean anything. */
+cl_status cl_report_bases_host(const uint8_t* h_codes, const uint64_t* h_off, uint64_t n, cl_report* acc);
+cl_status cl_report_quals_host(const cl_qual_params* qparams, const uint8_t* h_ascii_quals_in, const uint64_t* h_off, uint64_t n, cl_report* acc);
+cl_status cl_report_values_host(const uint8_t* h_ascii_values_out, const uint64_t* h_off, uint64_t n, cl_report* acc);
+/* Opt-in (off by default: one flag test per chunk, no launch, no allocation, every output byte the same).  While it is on,
+ * cl_compress_shard on this context and cl_compressor_encode of a compressor created on it add the report of every chunk's input —
+ * the arena and, with a quality stream, the input quality bytes — to the context's total, before the coders start.
+ * cl_ctx_report: the total so far (cleared when the flag is switched on). */
+void cl_ctx_set_report(cl_ctx* ctx, int on);
+cl_status cl_ctx_report(const cl_ctx* ctx, cl_report* out);
+
 /* ---- a14 + a16: CDNACoder / CEntrComprReads (dna_coder.{h,cpp}, entr_read.h:56-80) --------------------- */
 typedef struct cl_dna_coder cl_dna_coder;
 /* CDNACoder::Init(true, maxCandidates, level, ., n_ref_genome_pseudo_reads): one adaptive model set that
@@ -519,6 +557,8 @@ cl_status cl_compressor_verified_streams(const cl_compressor* c, uint64_t* parts
 cl_status cl_compressor_digest(const cl_compressor* c, cl_digest* dna, cl_digest* qual);
 /* cl_ctx_digest_values of the compressor's context (cl_ctx_set_digest_values) */
 cl_status cl_compressor_digest_values(const cl_compressor* c, cl_digest* out);
+/* cl_ctx_report of the compressor's context (cl_ctx_set_report): the report of the chunks encoded so far */
+cl_status cl_compressor_report(const cl_compressor* c, cl_report* out);
 
 /* cl_qual_coder_set_domain_symbols / cl_qual_coder_domains of the compressor's quality coder.  The setting must be made before the
  * first cl_compressor_encode or cl_compressor_prepare_parts call (CL_E_INVALID afterwards, and without a quality stream); the `dna`
