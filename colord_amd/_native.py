@@ -166,6 +166,8 @@ _SIG = {
     "cl_qual_coder_free": (None, [_P]),
     "cl_qual_coder_set_domain_symbols": (C.c_int32, [_P, C.c_uint64]),
     "cl_qual_coder_domains": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cl_qual_coder_model": (C.c_int32, [_P, C.c_uint32, C.c_uint64, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "cl_qual_coder_groups": (C.c_int32, [_P, C.POINTER(C.c_uint64)]),
     "cl_compressor_set_qual_domain_symbols": (C.c_int32, [_P, C.c_uint64]),
     "cl_compressor_qual_domains": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cl_qual_decode_domains": (C.c_int32, [_P, C.POINTER(QualParams), _P, _P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint64, _P, C.c_uint64]),

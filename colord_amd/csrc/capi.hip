@@ -147,6 +147,11 @@ extern "C" cl_status cl_dna_coder_model(const cl_dna_coder* d, uint32_t family, 
 	if (!d || !out) return CL_E_INVALID;
 	return cl_dna_model_read(d, family, context, out);
 }
+extern "C" cl_status cl_qual_coder_model(const cl_qual_coder* q, uint32_t family, uint64_t context, uint32_t* out, uint32_t cap, uint32_t* n_out)
+{
+	if (!q || !out || !n_out) return CL_E_INVALID;
+	return cl_qual_model_read(q, family, context, out, cap, n_out);
+}
 extern "C" void cl_ctx_set_verify_streams(cl_ctx* c, int on) { if (c) c->verify_streams = on != 0; }
 extern "C" cl_status cl_ctx_verified_streams(const cl_ctx* c, uint64_t* parts, uint64_t* symbols, uint64_t* bytes)
 {

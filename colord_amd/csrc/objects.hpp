@@ -80,6 +80,7 @@ void cl_dna_walked_free(DnaWalked* W);
 void cl_dna_set_ahead(cl_dna_coder* D, DnaWalked* W);               // takes W: the next cl_dna_encode uses it if it is the batch it was made for
 void cl_dna_coder_state(const cl_dna_coder* D, uint32_t* prev_types, uint32_t* read_id);
 cl_status cl_dna_model_read(const cl_dna_coder* D, uint32_t family, uint64_t context, uint32_t* out);   // behind cl_dna_coder_model (capi.hip)
+cl_status cl_qual_model_read(const cl_qual_coder* Q, uint32_t family, uint64_t context, uint32_t* out, uint32_t cap, uint32_t* n_out);   // behind cl_qual_coder_model (capi.hip)
 // the read-type history a batch hands to the next one (types of its last four reads after `prev_types`): from the first tuple of those reads alone
 cl_status cl_dna_batch_types(cl_ctx* ctx, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t es_bytes, uint32_t prev_types, uint32_t* out);
 // the same for the quality coder (qual.hip): symbols, sort by context, context runs of a batch, on any context

@@ -49,6 +49,7 @@ struct cl_qual_coder {
 	DevBuf<uint32_t> state;       // per-base family: n_ctx * (n_sym + 1)  (counters..., total)
 	DevBuf<uint32_t> bstate;      // byte family: 896 * 257
 	uint64_t symbols_coded = 0;
+	uint64_t groups_evolved = 0;  // groups of parts taken through the model kernels so far (cl_qual_coder_groups)
 	// model domains: dom_n symbols (0: none) close a domain at the next part boundary.  dom_since / parts_evolved / dom_first follow the
 	// model evolution (the one place the batches pass in order); prep_since is the preparation worker's own count, one batch after the
 	// other — a prepared batch whose count differs from the evolution's is made again (qual_evolve_batch)
@@ -471,6 +472,56 @@ extern "C" cl_status cl_qual_coder_domains(const cl_qual_coder* q, uint64_t* h_f
 	return CL_OK;
 }
 
+extern "C" cl_status cl_qual_coder_groups(const cl_qual_coder* q, uint64_t* n_out)
+{
+	if (!q || !n_out) return CL_E_INVALID;
+	*n_out = q->groups_evolved;
+	return CL_OK;
+}
+// cl_qual_coder_model (capi.hip): counters and total of one model as the last finished cl_qual_encode left them.  The per-base context
+// comes by its components and goes through the functions the encoder and the decoder share (qual_ctx.hpp); the dense id stays private.
+cl_status cl_qual_model_read(const cl_qual_coder* Q, uint32_t family, uint64_t context, uint32_t* out, uint32_t cap, uint32_t* n_out)
+{
+	cl_ctx* ctx = Q->ctx;
+	const QualCfg& c = Q->cfg;
+	if (Q->ahead || !Q->evolved.empty()) return cl_fail(ctx, CL_E_INVALID, "cl_qual_coder_model: a batch is prepared or evolved ahead");
+	const uint32_t* src = nullptr; uint32_t n_sym = 0;
+	if (family == 0)
+	{
+		if (c.mode == QM_AVERAGE || c.mode == QM_NONE) return cl_fail(ctx, CL_E_INVALID, "cl_qual_coder_model: this mode has no per-base family");
+		if ((context >> 24 & 0xff) || (context >> 41 & 0x7f) || (context >> 50)) return cl_fail(ctx, CL_E_INVALID, "cl_qual_coder_model: no such context");
+		const uint32_t missing = c.hist_radix - 1;
+		uint32_t hist = 0, place = 1;
+		for (uint32_t t = 0; t < 6; ++t)
+		{
+			const uint32_t f = (uint32_t)(context >> (4 * t)) & 0xfu;
+			if (t >= c.n_ctx_sym) { if (f) return cl_fail(ctx, CL_E_INVALID, "cl_qual_coder_model: more history fields than the mode has"); continue; }
+			if (f != 0xfu && f > missing - (c.mode == QM_ORIGINAL ? 0u : 1u)) return cl_fail(ctx, CL_E_INVALID, "cl_qual_coder_model: a history field beyond the mode's symbols");
+			hist = qual_hist_add(hist, place, f == 0xfu ? missing : f); place *= c.hist_radix;
+		}
+		const uint32_t b0 = (uint32_t)(context >> 32) & 3u, bm1 = (uint32_t)(context >> 34) & 3u, bm2 = (uint32_t)(context >> 36) & 3u, bp1 = (uint32_t)(context >> 38) & 3u;
+		const uint32_t i = (context >> 40 & 1) ? 2u : 0u;                        // (only `i > 1` enters a base context)
+		const uint32_t fl = (uint32_t)(context >> 48) & 3u;
+		if (fl && c.level <= 1) return cl_fail(ctx, CL_E_INVALID, "cl_qual_coder_model: flag bits at level 1");
+		const uint32_t id = qual_ctx_id(c, hist, qual_base_ctx(c, i, b0, bm1, bm2, bp1), fl);
+		if (id >= c.n_ctx) return cl_fail(ctx, CL_E_INVALID, "cl_qual_coder_model: no such context");
+		n_sym = c.n_sym; src = Q->state.p + (uint64_t)id * (n_sym + 1);
+	}
+	else if (family == 1)
+	{
+		if (context >= BYTE_CTX) return cl_fail(ctx, CL_E_INVALID, "cl_qual_coder_model: no such context");
+		n_sym = 256; src = Q->bstate.p + context * 257;
+	}
+	else return cl_fail(ctx, CL_E_INVALID, "cl_qual_coder_model: family 0 (per base) or 1 (average bytes)");
+	*n_out = n_sym + 1;
+	if (cap < n_sym + 1) return cl_fail(ctx, CL_E_CAPACITY, "cl_qual_coder_model: capacity");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	for (hipStream_t s : Q->cstreams) HIP_TRY(ctx, hipStreamSynchronize(s));
+	HIP_TRY(ctx, hipMemcpy(out, src, (size_t)(n_sym + 1) * 4, hipMemcpyDeviceToHost));
+	return CL_OK;
+}
+
 // CEntrComprQuals::Compress for a batch of whole parts (entr_qual.h:100-135).  Models persist across calls.
 namespace {
 cl_status qual_prepare(cl_ctx* ctx, cl_qual_coder* Q, const cl_reads* R, const uint8_t* d_quals, const uint64_t* d_qual_off,
@@ -504,7 +555,10 @@ cl_status qual_prepare(cl_ctx* ctx, cl_qual_coder* Q, const cl_reads* R, const u
 	// One group of parts = one sort + one range-coding launch.  The per-part interval chain is latency bound (its
 	// duration is set by the longest part, not by the number of parts), so groups are made as large as 32-bit
 	// symbol indices allow: every extra launch would pay that latency again.
-	const uint64_t GROUP_SYMS = (1ull << 31) - (1ull << 24);
+	// (COLORD_HIP_QUAL_GROUP_SYMS, read per call: a smaller group for tests, which reach a group cut inside a call at no other size.
+	// A part larger than the setting is still a group of its own; no output byte depends on it.)
+	uint64_t GROUP_SYMS = (1ull << 31) - (1ull << 24);
+	if (const char* e = getenv("COLORD_HIP_QUAL_GROUP_SYMS")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 1 && v < GROUP_SYMS) GROUP_SYMS = v; }
 	const bool per_base = !(c.mode == QM_AVERAGE);
 	auto syms_of = [&](uint32_t a, uint32_t b) { return (per_base ? (qo[b] - qo[a]) : 0) + (uint64_t)(h_part_bounds[b] - h_part_bounds[a]) * c.navg; };
 	// model domains: a part opens a new one when the open domain has reached dom_n symbols.  A group never spans a domain start: the
@@ -675,6 +729,7 @@ cl_status qual_evolve_batch(cl_ctx* ctx, cl_qual_coder* Q, const cl_reads* R, co
 			HIP_TRY(ctx, e2);
 		}
 		E.groups.push_back(std::move(Pn));
+		++Q->groups_evolved;
 	}
 	Q->dom_since = Pp->since_out; Q->parts_evolved += n_parts;
 	return CL_OK;

@@ -708,6 +708,19 @@ class QualCoder(_Obj):
         """cl_qual_coder_domains: the first part of every model domain so far, counted over the coder's lifetime."""
         return _domain_list(self.ctx, self.ctx.lib.cl_qual_coder_domains, self.h)
 
+    def model(self, family: int, context: int) -> np.ndarray:
+        """cl_qual_coder_model: the counters and, last, the total of one adaptive model after the last encode()."""
+        out = np.zeros(257, np.uint32)
+        n = C.c_uint32(0)
+        _check(self.ctx, self.ctx.lib.cl_qual_coder_model(self.h, family, context, out.ctypes.data, len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def groups(self) -> int:
+        """cl_qual_coder_groups: the groups of parts taken through the model kernels so far."""
+        n = C.c_uint64(0)
+        _check(self.ctx, self.ctx.lib.cl_qual_coder_groups(self.h, C.byref(n)))
+        return n.value
+
 
 def _domain_list(ctx, fn, h):
     n = C.c_uint64(0)

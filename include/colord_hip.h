@@ -248,6 +248,22 @@ cl_status cl_qual_encode(cl_ctx* ctx, cl_qual_coder* q, const cl_reads* reads, c
  * *n_out = their number, CL_E_CAPACITY if it exceeds cap (nothing is written then). */
 cl_status cl_qual_coder_set_domain_symbols(cl_qual_coder* q, uint64_t n);
 cl_status cl_qual_coder_domains(const cl_qual_coder* q, uint64_t* h_first_part, uint64_t cap, uint64_t* n_out);
+/* Test access: out[0 .. n_sym) = the counters and out[n_sym] = the total of one adaptive model as the last finished cl_qual_encode left
+ * them (all ones before its first symbol); *n_out = n_sym + 1, CL_E_CAPACITY if that exceeds cap.
+ * family 0, the per-base models (2, 4, 5 or 96 symbols): the context by its components, never by the library's private id —
+ *   bits 0-23   the history fields, four bits each, the field of the position before in bits 0-3: the symbol coded there (org: its
+ *               quantised class), 0xF where the read has no such position; fields the mode does not have are 0
+ *   bits 32-39  the bases b0 (this position, bits 32-33), bm1, bm2 (the one and two before, 0 where there is none), bp1 (the one
+ *               behind, 0 at the read's end), N as A; bit 40: the position is the read's third or a later one
+ *   bits 48-49  levels 2 and 3: 1 = unit match ('M'), 2 = inside an anchor ('A')
+ * family 1, the 256-symbol models of the average bytes: context = bin * 128 + floor(average of the bin before) for a high byte
+ * (avg: 0), 640 + high byte for a low byte.
+ * Waits for the context's stream and the coder's own; CL_E_INVALID for an unknown family or context, or while a batch is prepared or
+ * evolved ahead.
+ * cl_qual_coder_groups: the groups of parts the coder has taken through its model kernels so far (one per call unless a call holds a
+ * domain start or more symbols than a group may: 2^31 - 2^24, or COLORD_HIP_QUAL_GROUP_SYMS, read per call, which changes no byte). */
+cl_status cl_qual_coder_model(const cl_qual_coder* q, uint32_t family, uint64_t context, uint32_t* out, uint32_t cap, uint32_t* n_out);
+cl_status cl_qual_coder_groups(const cl_qual_coder* q, uint64_t* n_out);
 
 /* ---- a8: m-mer anchors (encoder.cpp:291-493,617-776,1016-1111,1149-1192,1577-1622) ------------------------ */
 typedef struct cl_anchors cl_anchors;

@@ -75,6 +75,8 @@ void orc_qual_free(orc_qual*);
 void orc_qual_encode(orc_qual*, const uint8_t* bases, const uint8_t* qual, uint32_t len, const uint8_t* flags);
 /* closes the current part (Finish/GetOutput/Restart, entr_qual.h:68-79); dst==NULL only returns the size */
 size_t orc_qual_finish_part(orc_qual*, uint8_t* dst, size_t cap);
+/* test access: counters and total (out[n_sym]) of one model; family 0 per base, 1 average bytes; the context as cl_qual_coder_model takes it; returns n_sym (0: bad family / cap) */
+uint32_t orc_qual_model(orc_qual*, int family, uint64_t context, uint32_t* out, uint32_t cap);
 void orc_qual_set_input(orc_qual*, const uint8_t* data, size_t n);
 void orc_qual_decode(orc_qual*, const uint8_t* bases, uint32_t len, const uint8_t* flags, uint8_t* qual_out);
 /* per-base 'A'/'M'/' '/'P' classes from a read's tuple stream (quality_coder_impl.cpp:25-75) */

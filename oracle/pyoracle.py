@@ -54,6 +54,8 @@ def lib():
         L.orc_qual_encode.argtypes = [C.c_void_p, u8p, u8p, C.c_uint32, C.c_void_p]
         L.orc_qual_finish_part.restype = C.c_size_t
         L.orc_qual_finish_part.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.orc_qual_model.restype = C.c_uint32
+        L.orc_qual_model.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint32]
         L.orc_qual_set_input.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.orc_qual_decode.argtypes = [C.c_void_p, u8p, C.c_uint32, C.c_void_p, u8p]
         L.orc_es_flags.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, u8p]
@@ -193,6 +195,15 @@ class QualCoder:
         buf = np.zeros(n, np.uint8)
         m = lib().orc_qual_finish_part(self.h, buf.ctypes.data, n)
         return buf[:m].tobytes()
+
+    def model(self, family: int, context: int) -> np.ndarray:
+        """Counters and, last, the total of one model (family 0 per base, 1 average bytes; the context as cl_qual_coder_model takes it);
+        all ones for a context never coded."""
+        out = np.zeros(257, np.uint32)
+        n = lib().orc_qual_model(self.h, family, context, out.ctypes.data, len(out))
+        if not n:
+            raise ValueError(f"no quality model family {family} / context {context:#x}")
+        return out[:n + 1].copy()
 
     def set_input(self, data: bytes):
         self._keep = (C.c_char * max(1, len(data))).from_buffer_copy(data or b"\0")

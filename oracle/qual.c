@@ -205,6 +205,51 @@ void orc_qual_encode(orc_qual* q, const uint8_t* b, const uint8_t* qual, uint32_
 	}
 }
 
+/* Test access: counters and total (out[n_sym]) of one model, all ones for a context never coded.  The context is given as
+ * cl_qual_coder_model takes it (include/colord_hip.h) and turned into the reference's own value here: family 0 by the history fields
+ * (0xF = no such position: the all-ones field of reset_context), the bases b0 / bm1 / bm2 / bp1, "third position or later" and the
+ * flag bits; family 1 by bin * 128 + floor(previous average) or 640 + high byte.  Returns n_sym (0: bad family / mode / cap). */
+uint32_t orc_qual_model(orc_qual* q, int family, uint64_t context, uint32_t* out, uint32_t cap)
+{
+	orc_ctxmap* c; uint64_t ctx;
+	if (family == 0)
+	{
+		if (q->mode == QM_AVERAGE || q->mode == QM_NONE) return 0;
+		c = &q->sym_map;
+		uint64_t hist = 0;
+		for (uint32_t t = 0; t < q->n_ctx_sym; ++t)
+		{
+			uint64_t f = (context >> (4 * t)) & 0xf;
+			if (f == 0xf) f = (1ULL << q->bits_per_sym) - 1;
+			hist |= f << (q->bits_per_sym * t);
+		}
+		const uint64_t b0 = (context >> 32) & 3, bm1 = (context >> 34) & 3, bm2 = (context >> 36) & 3, bp1 = (context >> 38) & 3, later = (context >> 40) & 1;
+		const uint64_t fl = q->level > 1 ? (context >> 48) & 3 : 0;
+		uint32_t sh = q->ctx_bits;
+		const int is_avg = q->mode == QM_QUINARY_AVG || q->mode == QM_QUAD_AVG || q->mode == QM_BINARY_AVG;
+		ctx = hist;
+		if (is_avg) { ctx += ((bm2 << 6) | (bm1 << 4) | (b0 << 2) | bp1) << sh; sh += 8; }                 /* quality_coder_impl.cpp:159-172 */
+		else if (q->mode != QM_ORIGINAL || q->level == 3) { ctx += (b0 | (bm1 << 2) | (bm2 << 4) | (bp1 << 6)) << sh; sh += 8; }   /* :323-339, :88-108 */
+		else { ctx += (b0 | (bm1 << 2) | ((uint64_t)(later && bm2 == bm1) << 4) | (bp1 << 5)) << sh; sh += 7; }
+		ctx += fl << sh;
+	}
+	else if (family == 1)
+	{
+		if (context >= 896) return 0;
+		c = &q->byte_map;
+		if (context >= 640) ctx = 0x100ULL + (context - 640);
+		else if (q->mode == QM_AVERAGE) ctx = 0;                                                           /* (:438-450; only context 0 is ever coded) */
+		else ctx = (1ULL << 30) + ((context / 128) << 24) + ((context % 128) << 16);
+		if (q->mode == QM_AVERAGE && context && context < 640) ctx = ~1ULL;                                /* never coded */
+	}
+	else return 0;
+	if (cap < c->n_sym + 1) return 0;
+	size_t h = orc_ctxmap_find(c, ctx);
+	for (uint32_t i = 0; i < c->n_sym; ++i) out[i] = h == (size_t)-1 ? 1u : c->pool[h * c->n_sym + i];
+	out[c->n_sym] = h == (size_t)-1 ? c->n_sym : c->totals[h];
+	return c->n_sym;
+}
+
 /* Finish + GetOutput + Restart (entr_qual.h:68-79): returns the part payload and starts a new one.
  * Models persist. */
 size_t orc_qual_finish_part(orc_qual* q, uint8_t* dst, size_t cap)
