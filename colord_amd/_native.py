@@ -56,6 +56,18 @@ class Report(C.Structure):
         return out
 
 
+class Edits(C.Structure):
+    """cl_edits: the edit-operation profile; every field is an unsigned 64-bit counter that adds over disjoint sets of reads."""
+    _fields_ = [("reads", C.c_uint64), ("bases", C.c_uint64), ("kind_reads", C.c_uint64 * 3), ("kind_bases", C.c_uint64 * 3), ("kind_bytes", C.c_uint64 * 3),
+                ("main_rev", C.c_uint64 * 2), ("tuples", C.c_uint64 * 8), ("anchor_bases", C.c_uint64), ("anchor_len_hist", C.c_uint64 * 29),
+                ("skip_entries", C.c_uint64), ("skip_entry_sum", C.c_uint64), ("skip_bases", C.c_uint64), ("skip_len_hist", C.c_uint64 * 29),
+                ("ins_base", C.c_uint64 * 4), ("del_base", C.c_uint64 * 4), ("match_base", C.c_uint64 * 4), ("sub", (C.c_uint64 * 4) * 4),
+                ("ins_run_hist", C.c_uint64 * 17), ("del_run_hist", C.c_uint64 * 17), ("identity_hist", C.c_uint64 * 101), ("identity_none", C.c_uint64),
+                ("alt_hist", C.c_uint64 * 65)]
+
+    as_dict = Report.as_dict
+
+
 _P = C.c_void_p
 class CompressParams(C.Structure):
     _fields_ = [("k", C.c_uint32), ("f", C.c_uint32), ("ci", C.c_uint32), ("cs", C.c_uint32), ("c", C.c_uint32),
@@ -114,6 +126,14 @@ _SIG = {
     "cl_ctx_set_report": (None, [_P, C.c_int]),
     "cl_ctx_report": (C.c_int32, [_P, C.POINTER(Report)]),
     "cl_compressor_report": (C.c_int32, [_P, C.POINTER(Report)]),
+    "cl_edits_clear": (None, [C.POINTER(Edits)]),
+    "cl_edits_add": (None, [C.POINTER(Edits), C.POINTER(Edits)]),
+    "cl_edit_profile": (C.c_int32, [_P, _P, _P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(Edits)]),
+    "cl_edit_profile_host": (C.c_int32, [_P, _P, C.c_uint32, _P, _P, C.c_uint64, C.POINTER(Edits), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "cl_edit_profile_error": (C.c_char_p, [C.c_uint32]),
+    "cl_ctx_set_edit_profile": (None, [_P, C.c_int]),
+    "cl_ctx_edit_profile": (C.c_int32, [_P, C.POINTER(Edits)]),
+    "cl_compressor_edit_profile": (C.c_int32, [_P, C.POINTER(Edits)]),
     "cl_digest_bases": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(Digest)]),
     "cl_digest_quals": (C.c_int32, [_P, C.POINTER(QualParams), _P, _P, _P, C.c_uint64, C.POINTER(Digest)]),
     "cl_digest_bases_host": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(Digest)]),

@@ -203,6 +203,7 @@ int run_compress(int argc, char** argv)
 	if (digest_values) cl_ctx_set_digest_values(ctx, 1);
 	check_report_options(O, with_qual);
 	if (O.report) cl_ctx_set_report(ctx, 1);
+	if (O.edit_profile) cl_ctx_set_edit_profile(ctx, 1);
 	std::vector<uint64_t> report_lens;                          // --report: every read length, as the reader hands the reads over in pass 1 (N50 / N90)
 	ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, nullptr, estimated_bases(R), &cmp), "cl_compressor_create");
 	if (O.qual_domain_symbols)
@@ -336,6 +337,12 @@ int run_compress(int argc, char** argv)
 		ReportSet S;
 		ck(ctx, cl_compressor_report(cmp, S.r.get()), "cl_compressor_report");
 		add_report(ar, S, report_lens, n, total, with_qual && O.P.qual_mode != 8);
+	}
+	if (O.edit_profile)
+	{
+		EditsSet E;
+		ck(ctx, cl_compressor_edit_profile(cmp, E.e.get()), "cl_compressor_edit_profile");
+		add_edits(ar, E, n, total);
 	}
 	if (O.qual_domain_symbols)
 	{

@@ -8,6 +8,7 @@
 #include "genome_io.hpp"
 #include "digest_stream.hpp"
 #include "report_stream.hpp"
+#include "edits_stream.hpp"
 #include <ctime>
 #include <mutex>
 
@@ -320,6 +321,14 @@ inline void add_report(ArchiveWriter& ar, ReportSet& S, const std::vector<uint64
 	S.n50 = rp_nxx(lens, 50); S.n90 = rp_nxx(lens, 90);
 	const std::vector<uint8_t> b = S.pack();
 	ar.add(ar.reg("hipreport"), b.data(), b.size(), 0);
+}
+// --edit-profile: the `hipedits` stream (edits_stream.hpp), before finish_archive: what the compressors' contexts and their lanes counted of the tuple
+// streams; it must be every read of the input
+inline void add_edits(ArchiveWriter& ar, const EditsSet& S, uint64_t n_reads, uint64_t n_bases)
+{
+	if (S.e->reads != n_reads || S.e->bases != n_bases) die("internal: the edit profile did not see every read");
+	const std::vector<uint8_t> b = S.pack();
+	ar.add(ar.reg("hipedits"), b.data(), b.size(), 0);
 }
 // --report with a *-fix mode: the -D values must be qualities the report can index
 inline void check_report_options(const Options& O, bool with_qual)

@@ -20,6 +20,7 @@ struct RankOut {
 	uint64_t n_reads = 0, mean_read_len = 0; uint32_t sparse_range = 0, n_refs = 0; cl_kmer_stats ks{};
 	uint64_t dna_base = 0, qual_base = 0, qual_framed = 0;     // where its framed `dna` / `qual` parts start in the file; bytes of the latter
 	uint64_t moved = 0;
+	std::unique_ptr<cl_edits> edits;                           // --edit-profile: what this rank's compressor and its lanes counted of their tuple streams
 	std::unique_ptr<cl_report> report;                         // --report: what this rank's compressor counted of its reads
 	cl_digest dig[3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } }, dig_all[3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } };      // --digest: dna / qual / (--digest-values) qual-values of this rank's reads; of all ranks (as gathered with the byte counts)
 };
@@ -118,6 +119,7 @@ int run_compress_multi(const Options& O)
 		const bool digest_qual = with_qual && O.P.qual_mode != 8;
 		if (O.digest && !independent) cl_ctx_set_digest(ctx, 1);
 		if (digest_values && !independent) cl_ctx_set_digest_values(ctx, 1);
+		if (O.edit_profile) cl_ctx_set_edit_profile(ctx, 1);
 		if (O.report) cl_ctx_set_report(ctx, 1);                            // (the report has no read indices: a rank's and an independent domain's compressor count alike)
 		ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, T ? &X : nullptr, my_bases, &cmp), "cl_compressor_create");
 		if (GM.on) GM.count_kmers(ctx, cmp);
@@ -204,6 +206,7 @@ int run_compress_multi(const Options& O)
 		// where this rank's parts go: an all-gather of the framed byte counts, an exclusive sum, pwrite — `dna` of all ranks first, then `qual`
 		if (O.digest && !independent) ck(ctx, cl_compressor_digest(cmp, &RO.dig[0], &RO.dig[1]), "cl_compressor_digest");
 		if (digest_values && !independent) ck(ctx, cl_compressor_digest_values(cmp, &RO.dig[2]), "cl_compressor_digest_values");
+		if (O.edit_profile) { RO.edits.reset(new cl_edits); ck(ctx, cl_compressor_edit_profile(cmp, RO.edits.get()), "cl_compressor_edit_profile"); }
 		if (O.report) { RO.report.reset(new cl_report); ck(ctx, cl_compressor_report(cmp, RO.report.get()), "cl_compressor_report"); }
 		// framed bytes of `dna`, `qual`; the content digests travel with them (--digest-values: the fourth triple too, 11 values instead of 8)
 		uint64_t mine[11] = { 0, 0, RO.dig[0].reads, RO.dig[0].symbols, RO.dig[0].sum, RO.dig[1].reads, RO.dig[1].symbols, RO.dig[1].sum, RO.dig[2].reads, RO.dig[2].symbols, RO.dig[2].sum };
@@ -298,6 +301,12 @@ int run_compress_multi(const Options& O)
 		for (uint32_t r = 0; r < world; ++r) if (out[r].report) rp_add(rep.r.get(), out[r].report.get());
 		std::vector<uint64_t> lens(n); for (uint64_t i = 0; i < n; ++i) lens[i] = S.len(i);
 		add_report(ar, rep, lens, n, total, with_qual && O.P.qual_mode != 8);
+	}
+	if (O.edit_profile)
+	{	// the ranks' (domains') profiles added, as the reports are
+		EditsSet E;
+		for (uint32_t r = 0; r < world; ++r) if (out[r].edits) ed_add(E.e.get(), out[r].edits.get());
+		add_edits(ar, E, n, total);
 	}
 	finish_archive(ar, O, R, tot);
 	if (use_rccl) rccl.destroy_all();

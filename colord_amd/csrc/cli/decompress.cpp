@@ -4,6 +4,7 @@
 // archive has no `qual` stream.  No GPU is needed to decompress.  An archive with a `hipdigest` stream (digest_stream.hpp) is checked
 // against it while it is decoded; `check` decodes without writing and prints the digests.
 #include "reader.hpp"
+#include "edits_stream.hpp"
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <ctime>
@@ -107,9 +108,9 @@ struct DeviceQualDecoder {
 
 int run_info(int argc, char** argv)
 {
-	bool want_report = false, json = false; std::vector<std::string> pos;
-	for (int i = 2; i < argc; ++i) { const std::string a = argv[i]; if (a == "--report") want_report = true; else if (a == "--json") json = true; else pos.push_back(a); }
-	if (pos.size() != 1 || (json && !want_report)) { fprintf(stderr, "usage: colord_hip info [--report [--json]] archive.colord\n"); return 1; }
+	bool want_report = false, want_edits = false, json = false; std::vector<std::string> pos;
+	for (int i = 2; i < argc; ++i) { const std::string a = argv[i]; if (a == "--report") want_report = true; else if (a == "--edit-profile") want_edits = true; else if (a == "--json") json = true; else pos.push_back(a); }
+	if (pos.size() != 1 || (json && !want_report && !want_edits) || (want_report && want_edits)) { fprintf(stderr, "usage: colord_hip info [--report [--json]] [--edit-profile [--json]] archive.colord\n"); return 1; }
 	const std::string& path = pos[0];
 	ArchiveReader ar;
 	if (!ar.open(path)) die("cannot open archive: " + path);
@@ -120,6 +121,15 @@ int run_info(int argc, char** argv)
 		if (have == 0) die("no content report is stored in this archive (written without --report); `colord_hip check` prints what it decodes to");
 		if (have < 0) die("the archive's `hipreport` stream is not one this build reads");
 		if (json) print_report_json(stdout, S); else print_report(stdout, S, false);
+		return 0;
+	}
+	if (want_edits)
+	{	// the stored edit-operation profile alone, on stdout: nothing is decoded
+		ar.close();
+		EditsSet E; const int have = read_hipedits(path, E);
+		if (have == 0) die("no edit profile is stored in this archive (written without --edit-profile)");
+		if (have < 0) die("the archive's `hipedits` stream is not one this build reads");
+		if (json) print_edits_json(stdout, E); else print_edits(stdout, E);
 		return 0;
 	}
 	std::vector<uint8_t> b; uint64_t meta = 0;
@@ -137,6 +147,11 @@ int run_info(int argc, char** argv)
 		fprintf(stderr, "content report: %llu reads, %llu bases, N50 %llu, %s (`colord_hip info --report [--json]` prints it)\n", (unsigned long long)rep.r->reads, (unsigned long long)rep.r->bases, (unsigned long long)rep.n50,
 			rep.r->has_qual ? "input against stored quality values" : "no quality part");
 	else if (have < 0) fprintf(stderr, "content report: a `hipreport` stream this build cannot read\n");
+	EditsSet eds;
+	if (const int have = read_hipedits(path, eds); have > 0)
+		fprintf(stderr, "edit profile: %llu of %llu reads coded with an edit script, %llu aligned bases (`colord_hip info --edit-profile [--json]` prints it)\n", (unsigned long long)eds.e->kind_reads[2], (unsigned long long)eds.e->reads,
+			(unsigned long long)edits_derived(*eds.e).aligned);
+	else if (have < 0) fprintf(stderr, "edit profile: a `hipedits` stream this build cannot read\n");
 	return 0;
 }
 

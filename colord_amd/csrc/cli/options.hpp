@@ -40,6 +40,7 @@ struct Options {
 	bool digest = false;                            // --digest: content digests of the input (cl_ctx_set_digest; ids on the host) in a `hipdigest` stream
 	bool digest_values = false;                     // --digest-values: --digest and the qual-values digest (cl_ctx_set_digest_values); `hipdigest` version 2
 	bool report = false;                            // --report: the content report of the input (cl_ctx_set_report) in a `hipreport` stream
+	bool edit_profile = false;                      // --edit-profile: the edit-operation profile of the tuple streams (cl_ctx_set_edit_profile) in a `hipedits` stream
 	uint64_t qual_domain_symbols = 0;               // --qual-domain-symbols N: the quality models start afresh about every N symbols (cl_compressor_set_qual_domain_symbols; stream `hipqdomains`)
 	int gpus = 1; std::vector<int> gpu_list; std::string transport = "rccl";   // --gpus N [--gpu-list a,b,..] [--transport rccl|host]: reads sharded over N GPUs (run_compress_multi)
 	Preset P{}; QDef qd;                            // resolved by parse_options: the preset of source and priority with the options laid over it, the quality thresholds / representatives
@@ -50,7 +51,7 @@ inline void usage()
 {
 	fprintf(stderr,
 		"usage: colord_hip compress-ont|compress-pbhifi|compress-pbraw [options] input.fastq|fasta[.gz] output.colord\n"
-		"       colord_hip decompress [--ignore-digest] [--gpu N] archive.colord output.fastq\n       colord_hip check [--gpu N] archive.colord\n       colord_hip info [--report [--json]] archive.colord\n"
+		"       colord_hip decompress [--ignore-digest] [--gpu N] archive.colord output.fastq\n       colord_hip check [--gpu N] archive.colord\n       colord_hip info [--report [--json]] [--edit-profile [--json]] archive.colord\n"
 		"options (as the reference, arg_parse.cpp:455-640):\n"
 		"  -p,--priority ratio|balanced|memory   -k,--kmer-len K with -a,--anchor-len A (both or none)\n"
 		"  -q,--qual org|none|avg|2-fix|4-fix|5-fix|2-avg|4-avg|5-avg   -T,--qual-thresholds a,b,..   -D,--qual-values a,b,..\n"
@@ -88,6 +89,15 @@ inline void usage()
 		"                     archive and is not checked.  Same report with any --part-symbols, --stream-input, -G [-s], --domains, --gpus: all of them read the input through one reader in\n"
 		"                     one process, which has every read length for N50 / N90.  A *-fix mode needs -D values <= 95.  With -q none or FASTA input there is no quality part.\n"
 		"                     Cost: one pass over 0.375 bytes per base and one over the quality bytes per chunk, two in the *-avg modes (not measured on a GPU yet)\n"
+		"  --edit-profile     what the compressor did with the bases, counted on the device from every read's edit script right after it was made, is stored in the archive (stream `hipedits`,\n"
+		"                     2504 bytes; the reference's decompressor ignores it): reads coded plain / with an edit script, tuples by type, anchor and skip lengths, the substitution matrix,\n"
+		"                     inserted, deleted and matched base composition, insertion and deletion run lengths, identity per read, alternative references per read.  `colord_hip info\n"
+		"                     --edit-profile [--json]` prints it without decoding anything, with the rates per aligned base, transitions : transversions and the identity median.  THIS IS THE\n"
+		"                     DIVERGENCE BETWEEN A READ AND THE REFERENCE READS IT WAS CODED AGAINST, and both carry errors: it is not a per-read error rate, except against the pseudo reads\n"
+		"                     of -G; and it covers only what the encoder aligned (plain reads and skipped stretches say nothing).  `decompress` / `check` do not recompute it.  Works with\n"
+		"                     --stream-input, -G [-s], --part-symbols, --chunk-bases; with --gpus / --domains every domain has its own reference reads and the parts are added.\n"
+		"                     Cost: one pass over the tuple bytes per chunk; measured on an MI355X: 2.17 ms of kernel time for a 5-Mbase ONT chunk (1 025 reads, 3.8 MB of tuples), next to 2.31 ms of\n"
+		"                     the --verify-scripts pass and 753 ms of all kernels of that chunk (DESIGN.md 9)\n"
 		"  --qual-domain-symbols N   model domains of the QUALITY stream alone: its adaptive models start afresh at the first part boundary at which a domain holds N coded\n"
 		"                     symbols, and the starts are recorded (stream `hipqdomains`).  `colord_hip decompress --gpu N` / `check --gpu N` then decode the domains side by\n"
 		"                     side on the device, one lane each; without --gpu they decode on the host as one chain that starts afresh at every domain.  The k-mer set, the\n"
@@ -154,6 +164,7 @@ inline Options parse_options(int argc, char** argv)
 		else if (a == "--digest") O.digest = true;
 		else if (a == "--digest-values") O.digest = O.digest_values = true;
 		else if (a == "--report") O.report = true;
+		else if (a == "--edit-profile") O.edit_profile = true;
 		else if (a == "--parse-threads") { O.parse_threads = atoi(need(i).c_str()); if (O.parse_threads < 1 || O.parse_threads > 256) die("--parse-threads must be in [1, 256]"); }
 		else if (a == "-h" || a == "--help") { usage(); exit(0); }
 		else if (!a.empty() && a[0] == '-' && a.size() > 1) die("unknown option " + a);

@@ -352,6 +352,9 @@ struct cl_ctx {
 	cl_digest digest_qval{ 0, 0, 0 };
 	bool report = false;                         // cl_ctx_set_report: the same calls add the content report of their input (report.hip)
 	cl_report* report_acc = nullptr;             // the total so far (owner thread only); made when the flag is first switched on, freed with the context
+	bool edit_profile = false;                   // cl_ctx_set_edit_profile: tuple_streams (pass_steps.hpp) adds the edit-operation profile of every batch it makes (edits.hip)
+	cl_edits* edits_acc = nullptr;               // the total of the batches made on THIS context (under edits_mu: cl_ctx_edit_profile reads the encode lanes' from the owner's thread); freed with the context
+	mutable std::mutex edits_mu;
 	uint64_t gap_paths[11] = { 0 };              // cl_ctx_gap_paths: the last cl_encode_reads' gaps per size class 0..7, quad -> wave, giant -> wave, wave-pool redo rounds (owner thread only)
 	std::map<std::string, KernelTime> times;     // per-kernel accumulated HIP-event time of the last API call
 	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;

@@ -146,7 +146,8 @@ inline cl_status tuple_streams(cl_ctx* ctx, const cl_compress_params* P, Handle<
 	const uint64_t es_cap = reads->total_bases + 16ull * n + 4096;
 	DEV_ALLOC(ctx, out.es, es_cap); DEV_ALLOC(ctx, out.es_off, (uint64_t)n + 1); DEV_ALLOC(ctx, out.es_nt, n);
 	CL_TRY(cl_encode_reads(ctx, reads, refs, anc, cc, P->anchor_len, P->min_part_alt, max_rec, P->cost_mult, h_pack_bounds, n_packs, out.es.p, es_cap, out.es_off.p, out.es_nt.p, &out.es_bytes));
-	return ctx->verify ? verify_streams(ctx, reads, refs, out) : CL_OK;
+	if (ctx->verify) CL_TRY(verify_streams(ctx, reads, refs, out));
+	return ctx->edit_profile ? edit_profile_chunk(ctx, refs, out.es.p, out.es_off.p, n) : CL_OK;
 }
 
 // The coder tail of a batch: a14 + a16 the DNA stream, a13 + a15 the quality stream.  The quality stream of level 1 does not depend on

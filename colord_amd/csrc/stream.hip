@@ -442,6 +442,10 @@ extern "C" cl_status cl_compressor_report(const cl_compressor* c, cl_report* out
 }
 
 // every context that codes for the compressor: its own (the DNA stream; the quality stream of levels 2 and 3) and the quality coder's
+extern "C" cl_status cl_compressor_edit_profile(const cl_compressor* c, cl_edits* out)
+{
+	return c ? cl_ctx_edit_profile(c->ctx, out) : CL_E_INVALID;
+}
 extern "C" cl_status cl_compressor_verified_streams(const cl_compressor* c, uint64_t* parts, uint64_t* symbols, uint64_t* bytes)
 {
 	if (!c) return CL_E_INVALID;

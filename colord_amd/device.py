@@ -55,7 +55,8 @@ class _OrderedLib:
                   "cl_ctx_set_digest", "cl_ctx_digest", "cl_compressor_digest", "cl_digest_bases_host", "cl_digest_bytes_host", "cl_qual_decoder_set_digest", "cl_qual_decoder_digest",
                   "cl_ctx_set_digest_values", "cl_ctx_digest_values", "cl_compressor_digest_values", "cl_qual_values_host", "cl_digest_qual_values_host",
                   "cl_qual_coder_domains", "cl_compressor_qual_domains", "cl_ctx_gap_paths",
-                  "cl_report_clear", "cl_report_add", "cl_report_bases_host", "cl_report_quals_host", "cl_report_values_host", "cl_ctx_set_report", "cl_ctx_report", "cl_compressor_report")
+                  "cl_report_clear", "cl_report_add", "cl_report_bases_host", "cl_report_quals_host", "cl_report_values_host", "cl_ctx_set_report", "cl_ctx_report", "cl_compressor_report",
+                  "cl_edits_clear", "cl_edits_add", "cl_edit_profile_host", "cl_edit_profile_error", "cl_ctx_set_edit_profile", "cl_ctx_edit_profile", "cl_compressor_edit_profile")
 
     def __init__(self, lib, device):
         self._lib, self._device, self._cache = lib, device, {}
@@ -191,6 +192,28 @@ class Context:
         r = N.Report()
         _check(None, self.lib.cl_ctx_report(self.h, C.byref(r)))
         return r
+
+    def set_edit_profile(self, on: bool = True):
+        """cl_ctx_set_edit_profile: every batch of tuple streams made on this context or by a lane of its compressors adds its edit-operation profile
+        (cleared when switched on)."""
+        self.lib.cl_ctx_set_edit_profile(self.h, int(bool(on)))
+
+    def edit_profile(self) -> "N.Edits":
+        """cl_ctx_edit_profile: the profile so far of this context and its compressor's encode lanes."""
+        e = N.Edits()
+        _check(None, self.lib.cl_ctx_edit_profile(self.h, C.byref(e)))
+        return e
+
+    def edit_profile_of(self, refs: "Reads", es: torch.Tensor, es_off: torch.Tensor, flush_bytes: int = 0, max_blocks: int = 0, acc: "N.Edits | None" = None) -> "N.Edits":
+        """cl_edit_profile: the profile of the tuple streams es / es_off (n + 1 byte offsets) against the arena refs, added to acc.  A malformed
+        stream raises (CL_E_INVALID, the text names the first such read) and leaves acc as it is."""
+        es, es_off = es.contiguous(), es_off.contiguous()
+        if acc is None:
+            acc = N.Edits()
+            self.lib.cl_edits_clear(C.byref(acc))
+        n = max(es_off.numel() - 1, 0)
+        _check(self, self.lib.cl_edit_profile(self.h, refs.h, es.data_ptr() if es.numel() else None, es_off.data_ptr() if n else None, n, flush_bytes, max_blocks, C.byref(acc)))
+        return acc
 
     @staticmethod
     def new_report() -> "N.Report":
@@ -778,6 +801,12 @@ class Compressor(_Obj):
         d, q = N.Digest(), N.Digest()
         _check(None, self.ctx.lib.cl_compressor_digest(self.h, C.byref(d), C.byref(q)))
         return d.triple(), q.triple()
+
+    def edit_profile(self) -> "N.Edits":
+        """cl_compressor_edit_profile: the edit-operation profile of the chunks whose tuple streams are made (Context.set_edit_profile)."""
+        e = N.Edits()
+        _check(None, self.ctx.lib.cl_compressor_edit_profile(self.h, C.byref(e)))
+        return e
 
     def report(self) -> "N.Report":
         """cl_compressor_report: the content report of the chunks encoded so far (Context.set_report)."""

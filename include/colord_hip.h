@@ -416,6 +416,63 @@ cl_status cl_report_values_host(const uint8_t* h_ascii_values_out, const uint64_
 void cl_ctx_set_report(cl_ctx* ctx, int on);
 cl_status cl_ctx_report(const cl_ctx* ctx, cl_report* out);
 
+/* ---- edit-operation profile (no counterpart in the reference) — what the compressor did with the bases -------------- */
+/* Counted from the tuple streams of a batch (the output of cl_encode_reads) and the reference reads they point to.  THIS IS THE
+ * DIVERGENCE BETWEEN A READ AND THE REFERENCE READS IT WAS CODED AGAINST — earlier reads of the same input, and both carry
+ * sequencing errors.  It is NOT a per-read error rate, except against the pseudo reads of a reference genome (-G); and it covers
+ * only what the encoder aligned: reads coded plain, and the stretches an edit script skips, say nothing.
+ * Every counter is unsigned 64-bit and adds over disjoint sets of reads, in any order.
+ *   reads, bases            all reads of the batch and the bases their streams produce
+ *   kind_reads / kind_bases / kind_bytes [3]   reads, bases and stream bytes by first tuple: 0 start-plain, 1 start-plain-with-Ns,
+ *                           2 start-es (an edit script)
+ *   main_rev[2]             edit-script reads by the orientation nibble of their start-es tuple (0, not 0)
+ *   tuples[8]               tuples inside edit scripts by type 0..7: ins, del, match, subst, anchor, skip, alt-id, main-ref (the start
+ *                           tuple is not counted)
+ *   anchor_bases, anchor_len_hist[29]   sum of the anchor lengths; anchors by bit length of the length (0 -> 0, 1 -> 1, 2..3 -> 2, ..)
+ *   skip_entries, skip_entry_sum        skips whose preceding tuple in the stream is an alt-id: their value is the position at which the
+ *                           alternative is entered, not bases passed over
+ *   skip_bases, skip_len_hist[29]       every other skip: the sum of the values, and the skips by bit length of the value
+ *   ins_base[4]             inserted bases
+ *   del_base[4], match_base[4]          the reference base under the cursor, in the read's orientation (complemented on a reversed
+ *                           reference)
+ *   sub[from][to]           from = the reference base under the cursor, to = the read's base; the diagonal is 0
+ *   ins_run_hist[17], del_run_hist[17]  maximal runs of consecutive ins (del) tuples in one read's stream — any other tuple and the
+ *                           stream's end close a run — by min(length, 16); index 0 stays 0
+ *   identity_hist[101], identity_none   per edit-script read, m = matches + anchor bases, d = m + subst + ins + del: the read counts in
+ *                           bin floor(100 m / d), or in identity_none when d = 0
+ *   alt_hist[65]            edit-script reads by the number of DISTINCT alternative reference ids they use (0..64) */
+typedef struct cl_edits {
+	uint64_t reads, bases, kind_reads[3], kind_bases[3], kind_bytes[3], main_rev[2], tuples[8];
+	uint64_t anchor_bases, anchor_len_hist[29], skip_entries, skip_entry_sum, skip_bases, skip_len_hist[29];
+	uint64_t ins_base[4], del_base[4], match_base[4], sub[4][4], ins_run_hist[17], del_run_hist[17];
+	uint64_t identity_hist[101], identity_none, alt_hist[65];
+} cl_edits;
+void cl_edits_clear(cl_edits* e);
+void cl_edits_add(cl_edits* dst, const cl_edits* src);
+/* The profile of n_reads tuple streams (d_es / d_es_off: n_reads + 1 byte offsets, as cl_encode_reads writes them) against the arena
+ * `refs`, added to *acc (host).  On the device, a wave per read, the stream 64 bytes per step; anchors are not copied, so a read costs
+ * its stream bytes / 64 and one reference base per del, match or subst tuple.  Persistent blocks of four waves count into 32-bit
+ * cells in LDS, which are added to the 64-bit total at a block's end and whenever flush_bytes stream bytes or more were counted since
+ * the last time (0: the default, 2^30; clamped to 1 .. 2^32 - 2^16); max_blocks: the grid's bound (0: the default, four per CU).
+ * Both arguments change no result.  A malformed stream (empty, a bad first tuple, a type not allowed inside a script, a tuple that
+ * crosses the stream's end, an id or position outside the references, a base value out of range, a 65th alternative) is
+ * CL_E_INVALID, the text naming the first such read, and NOTHING of the batch is added; it never makes the kernel read out of range.
+ * CL_E_UNSUPPORTED: four consecutive reads of 2^32 or more stream bytes together (a 32-bit cell could wrap). */
+cl_status cl_edit_profile(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads,
+                          uint64_t flush_bytes, uint32_t max_blocks, cl_edits* acc);
+/* The same on the HOST, a sequential walk with the same checks and the same answers: reference read i = the base codes 0..3 at
+ * [h_ref_off[i], h_ref_off[i + 1]) of h_ref_codes.  bad_read / bad_code (optional): the first malformed read and what it ran into
+ * (cl_edit_profile_error names the code). */
+cl_status cl_edit_profile_host(const uint8_t* h_ref_codes, const uint64_t* h_ref_off, uint32_t n_refs, const uint8_t* h_es, const uint64_t* h_es_off,
+                               uint64_t n_reads, cl_edits* acc, uint64_t* bad_read, uint32_t* bad_code);
+const char* cl_edit_profile_error(uint32_t code);
+/* Opt-in (off by default: one flag test per batch, no launch, no allocation, every output byte the same).  While it is on, every
+ * batch of tuple streams made on this context — by cl_compress_shard, by cl_compressor_encode, or by an encode lane of a compressor
+ * created on it — adds its profile.  cl_ctx_edit_profile: the total so far of this context and its compressor's lanes (cleared when
+ * the flag is switched on). */
+void cl_ctx_set_edit_profile(cl_ctx* ctx, int on);
+cl_status cl_ctx_edit_profile(const cl_ctx* ctx, cl_edits* out);
+
 /* ---- a14 + a16: CDNACoder / CEntrComprReads (dna_coder.{h,cpp}, entr_read.h:56-80) --------------------- */
 typedef struct cl_dna_coder cl_dna_coder;
 /* CDNACoder::Init(true, maxCandidates, level, ., n_ref_genome_pseudo_reads): one adaptive model set that
@@ -575,6 +632,9 @@ cl_status cl_compressor_digest(const cl_compressor* c, cl_digest* dna, cl_digest
 cl_status cl_compressor_digest_values(const cl_compressor* c, cl_digest* out);
 /* cl_ctx_report of the compressor's context (cl_ctx_set_report): the report of the chunks encoded so far */
 cl_status cl_compressor_report(const cl_compressor* c, cl_report* out);
+/* cl_ctx_edit_profile of the compressor's context (cl_ctx_set_edit_profile): the profile of the chunks whose tuple streams are made,
+ * its encode lanes' included — after the last cl_compressor_encode, of every chunk */
+cl_status cl_compressor_edit_profile(const cl_compressor* c, cl_edits* out);
 
 /* cl_qual_coder_set_domain_symbols / cl_qual_coder_domains of the compressor's quality coder.  The setting must be made before the
  * first cl_compressor_encode or cl_compressor_prepare_parts call (CL_E_INVALID afterwards, and without a quality stream); the `dna`
