@@ -196,6 +196,10 @@ _SIG = {
     "cl_anchor_candidates_hifi": (C.c_int32, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, C.POINTER(_P)]),
     "cl_anchors_free": (None, [_P]),
     "cl_anchors_total": (C.c_uint64, [_P]),
+    "cl_anchors_wave_tasks": (C.c_uint64, [_P]),
+    "cl_anchors_wave_pairs": (C.c_uint64, [_P]),
+    "cl_anchors_lane_tasks": (C.c_uint64, [_P]),
+    "cl_anchors_lane_pairs": (C.c_uint64, [_P]),
     "cl_anchors_n_cands": (_P, [_P]),
     "cl_anchors_cands": (_P, [_P]),
     "cl_anchors_cand_offsets": (_P, [_P]),

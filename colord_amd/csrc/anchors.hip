@@ -27,6 +27,8 @@ struct cl_anchors {
 	DevBuf<uint32_t> cand;        // n_reads * c * 4: ref_id, rev, tot_anchor_len, n_anchors
 	DevBuf<uint64_t> cand_off;    // n_reads * c + 1: first anchor of each candidate slot
 	DevBuf<uint32_t> anchors;     // n_anchors * 3: len, pos_enc, pos_ref
+	DevBuf<unsigned long long> lis_counts_d;      // accumulated by the chaining kernels; copied to lis_counts at the end of the call
+	unsigned long long lis_counts[6] = { 0, 0, 0, 0, 0, 0 };   // non-empty tasks and their pairs chained by a wave; by a lane; wave form: elements that did not extend; longest list
 };
 
 namespace {
@@ -530,6 +532,24 @@ __global__ void k_task_pairs(const uint64_t* __restrict__ pairs, uint64_t n_pair
 	pair_cnt[t] = total;
 }
 
+// counters of the chaining kernels: LIS_COUNT_LINES lines of 8 (wave tasks, wave pairs, lane tasks, lane pairs, elements of the wave form
+// that did not extend, longest list, -, -), summed into line 0 at the end of the call
+constexpr uint32_t LIS_COUNT_LINES = 1024;
+__device__ inline unsigned long long shfl_xor_u64(unsigned long long v, int d)
+{
+	return ((unsigned long long)(uint32_t)__shfl_xor((int)(v >> 32), d, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64);
+}
+__global__ __launch_bounds__(64) void k_lis_counts_sum(unsigned long long* __restrict__ counts)
+{
+	unsigned long long v[6] = { 0, 0, 0, 0, 0, 0 };
+	for (uint32_t l = threadIdx.x; l < LIS_COUNT_LINES; l += 64)
+		for (int k = 0; k < 6; ++k) { const unsigned long long x = counts[(size_t)l * 8 + k]; v[k] = k == 5 ? max(v[k], x) : v[k] + x; }
+	for (int d = 32; d; d >>= 1)
+		for (int k = 0; k < 6; ++k) { const unsigned long long x = shfl_xor_u64(v[k], d); v[k] = k == 5 ? max(v[k], x) : v[k] + x; }
+	__syncthreads();                                                        // (every line is read before line 0 is written)
+	if (threadIdx.x == 0) for (int k = 0; k < 6; ++k) counts[k] = v[k];
+}
+
 // ---- A5: one lane per task: LIS (utils.cpp:157-209), map-back (encoder.cpp:644-658), MergeAnchors (:731-776) ----
 __device__ inline int lis_search(const int* __restrict__ tf, int size, int value)
 {
@@ -546,12 +566,25 @@ __device__ inline int lis_search(const int* __restrict__ tf, int size, int value
 __global__ __launch_bounds__(64) void k_lis_anchors(Arena A, Arena R, TaskCfg cfg, const uint32_t* __restrict__ cand_refs, uint32_t n_tasks,
                                                    const uint64_t* __restrict__ pair_off, const uint32_t* __restrict__ pair_cnt, const uint64_t* __restrict__ pairs,
                                                    int* __restrict__ tf, int* __restrict__ ts, int* __restrict__ pred,
-                                                   uint32_t* __restrict__ anch, uint32_t* __restrict__ t_nanch, uint32_t* __restrict__ t_tot, uint32_t dbg)
+                                                   uint32_t* __restrict__ anch, uint32_t* __restrict__ t_nanch, uint32_t* __restrict__ t_tot,
+                                                   uint32_t wave_min, unsigned long long* __restrict__ counts, uint32_t dbg)
 {
 	__builtin_amdgcn_s_setprio(3);                                          // a launch of this kernel lasts as long as its slowest chain: its waves go first on their SIMDs
 	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-	if (t >= n_tasks) return;
-	const uint64_t a = pair_off[t], b = a + pair_cnt[t];
+	const uint32_t n_own = t < n_tasks ? pair_cnt[t] : 0;
+	const bool others = n_own && wave_min && n_own >= wave_min;             // k_lis_anchors_wave's
+	{	// the counters: summed over the wave first, one line of counters per block number (atomics on one address queue up behind each other)
+		unsigned long long sum = others ? 0 : n_own; uint32_t mx = (uint32_t)sum;
+		for (int d = 32; d; d >>= 1) { sum += shfl_xor_u64(sum, d); mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64)); }
+		const uint32_t tasks = (uint32_t)__popcll(__ballot(n_own && !others));
+		if ((threadIdx.x & 63) == 0 && tasks)
+		{
+			unsigned long long* cl = counts + (size_t)(blockIdx.x % LIS_COUNT_LINES) * 8;
+			atomicAdd(cl + 2, (unsigned long long)tasks); atomicAdd(cl + 3, sum); atomicMax(cl + 5, (unsigned long long)mx);
+		}
+	}
+	if (t >= n_tasks || others) return;
+	const uint64_t a = pair_off[t], b = a + n_own;
 	uint32_t n_anch = 0, tot = 0;
 	if (b > a)
 	{
@@ -648,6 +681,197 @@ __global__ __launch_bounds__(64) void k_lis_anchors(Arena A, Arena R, TaskCfg cf
 		if (run) { out[3 * n_anch] = run + cfg.m - 1; out[3 * n_anch + 1] = start_e; out[3 * n_anch + 2] = start_r; tot += run + cfg.m - 1; ++n_anch; }
 	}
 	t_nanch[t] = n_anch; t_tot[t] = tot;
+}
+
+// ---- A5w: the same by a WAVE per task, for long lists ----
+// On long reads the pairs of a task are almost all collinear, and each of the three walks of k_lis_anchors is then a run of identical
+// steps; the wave takes 64 of them at once and falls back to the sequential rule where a step differs, so F / S / PR, the anchors and
+// the totals are those of the lane form.  What one lane writes and another reads (F, S, PR) goes through memory behind a
+// workgroup-scope fence: the lanes of a wave share their CU's L1.
+__device__ inline void lis_wave_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); }
+__device__ inline uint64_t shfl_u64(uint64_t v, uint32_t src)
+{
+	return ((uint64_t)(uint32_t)__shfl((int)(v >> 32), (int)src, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)v, (int)src, 64);
+}
+__device__ inline uint32_t ones_from_bit0(uint64_t b) { return b == ~0ULL ? 64u : (uint32_t)__builtin_ctzll(~b); }
+// lis_search (lower bound in the strictly increasing F[0..size)) as a 64-ary search: lane l probes the last element of the l-th of
+// 64 equal pieces, the count of probes below the value names the piece that holds the bound
+__device__ inline int lis_search_wave(const int* F, int size, int value, uint32_t lane)
+{
+	int lo = 0;
+	while (size > 0)
+	{
+		const int piece = (size + 63) >> 6, end = lo + size;
+		const long long idx = (long long)lo + ((long long)lane + 1) * piece - 1;
+		const bool less = idx < end && F[idx] < value;
+		lo += __popcll(__ballot(less)) * piece;
+		size = min(piece - 1, end - lo);
+	}
+	return lo;
+}
+constexpr uint32_t LIS_WAVE_GAP = 8;          // pairs between two chain elements that a lane checks itself in the map-back; above: the wave's scan
+constexpr uint32_t LIS_WAVE_BLOCK = 256;      // four tasks a block
+constexpr uint32_t LIS_WAVE_MIN_DEFAULT = 64; // pairs of a task from which a wave chains it (COLORD_HIP_LIS_WAVE_MIN)
+__global__ __launch_bounds__(LIS_WAVE_BLOCK) void k_lis_anchors_wave(Arena A, Arena R, TaskCfg cfg, const uint32_t* __restrict__ cand_refs, uint32_t n_tasks,
+                                                        const uint64_t* __restrict__ pair_off, const uint32_t* __restrict__ pair_cnt, const uint64_t* __restrict__ pairs,
+                                                        int* tf, int* ts, int* pred, uint32_t* __restrict__ anch, uint32_t* __restrict__ t_nanch, uint32_t* __restrict__ t_tot,
+                                                        uint32_t wave_min, unsigned long long* __restrict__ counts, uint32_t dbg)
+{
+	__builtin_amdgcn_s_setprio(3);                                          // as the lane form: a launch lasts as long as its slowest chain
+	const uint32_t lane = threadIdx.x & 63;
+	const uint32_t t = __builtin_amdgcn_readfirstlane(blockIdx.x * (LIS_WAVE_BLOCK / 64) + (threadIdx.x >> 6));
+	if (t >= n_tasks) return;
+	const uint32_t n = pair_cnt[t];
+	if (n == 0 || n < wave_min) return;                                     // the lane form's
+	const uint64_t a = pair_off[t];
+	const uint64_t* P = pairs + a;
+	int* F = tf + a; int* S = ts + a; int* PR = pred + a;
+	const uint32_t m = cfg.m, pr_mask = (1u << cfg.pr) - 1, pe_mask = (1u << cfg.pe) - 1;
+	auto ref_pos = [&](uint32_t i) -> int { return (int)(~(uint32_t)P[i] & pr_mask); };
+	auto enc_pos = [&](uint32_t i) -> uint32_t { return (uint32_t)(P[i] >> cfg.pr) & pe_mask; };
+	unsigned long long* cl = counts + (size_t)(blockIdx.x % LIS_COUNT_LINES) * 8;
+	if (lane == 0) { atomicAdd(cl, 1ULL); atomicAdd(cl + 1, (unsigned long long)n); atomicMax(cl + 5, (unsigned long long)n); }
+	uint32_t n_slow = 0;                                                    // elements that took the sequential rule (reported with COLORD_HIP_ANCHOR_DEBUG)
+	// forward pass: the longest prefix of the step that extends the chain is appended at once; the first element that does not takes the
+	// sequential rule (search, replace, predecessor) and the step resumes behind it
+	int out_len = 0, last_f = -1, last_s = -1;                              // (positions are >= 0: the first pair extends the empty chain, PR[0] = -1)
+	for (uint32_t i0 = 0; i0 < n; i0 += 64)
+	{
+		const uint32_t cnt = min(64u, n - i0);
+		const int x = lane < cnt ? ref_pos(i0 + lane) : 0;
+		const int xp = __shfl_up(x, 1, 64);
+		uint32_t k0 = 0;
+		while (k0 < cnt)                                                // every turn takes at least one element
+		{
+			const bool ext = lane >= k0 && lane < cnt && x > (lane == k0 ? last_f : xp);
+			const uint32_t r = ones_from_bit0(__ballot(ext) >> k0);
+			if (r)
+			{
+				if (lane >= k0 && lane < k0 + r)
+				{
+					F[out_len + (int)(lane - k0)] = x; S[out_len + (int)(lane - k0)] = (int)(i0 + lane);
+					PR[i0 + lane] = lane == k0 ? last_s : (int)(i0 + lane) - 1;
+				}
+				out_len += (int)r; k0 += r;
+				last_f = __shfl(x, (int)k0 - 1, 64); last_s = (int)(i0 + k0) - 1;
+			}
+			if (k0 < cnt)
+			{
+				const int xs = __shfl(x, (int)k0, 64);
+				lis_wave_fence();
+				const int pos = lis_search_wave(F, out_len, xs, lane);
+				const int before = pos > 0 ? S[pos - 1] : -1;
+				if (lane == 0) { F[pos] = xs; S[pos] = (int)(i0 + k0); PR[i0 + k0] = before; }
+				if (pos == out_len - 1) { last_f = xs; last_s = (int)(i0 + k0); }
+				++k0; ++n_slow;
+			}
+		}
+	}
+	if (lane == 0 && n_slow) atomicAdd(cl + 4, (unsigned long long)n_slow);
+	if (dbg == 1) { if (lane == 0) { t_nanch[t] = 0; t_tot[t] = 0; } return; }
+	// predecessor walk: the block of PR behind `cur`; where every predecessor is the pair before, that many F at once, then the jump
+	lis_wave_fence();
+	{
+		int cur = S[out_len - 1];
+		for (int i = out_len - 1; i >= 0; )
+		{
+			const int nv = min(64, i + 1);
+			const bool in = (int)lane < nv && cur - (int)lane >= 0;
+			const int pv = in ? PR[cur - (int)lane] : -2;
+			const int run = (int)ones_from_bit0(__ballot(in && pv == cur - (int)lane - 1));
+			const int last = min(run, nv - 1);                           // lanes 0..last hold chain elements i..i - last
+			if ((int)lane <= last) F[i - (int)lane] = cur - (int)lane;  // F[i] = pair index of chain element i
+			cur = __shfl(pv, last, 64);
+			i -= last + 1;
+		}
+	}
+	if (dbg == 2) { if (lane == 0) { t_nanch[t] = 0; t_tot[t] = 0; } return; }
+	// map-back + merge, 64 chain elements a step.  An element assumes that the scan starts just behind the element before (which hit at
+	// its own position) and hits at its own; it checks that on the distinct read positions in between, which are the ones the sequential
+	// scan would have tested.  The first element that cannot confirm this is scanned for by the wave from its true start, and the next
+	// step begins behind it.
+	lis_wave_fence();
+	const uint32_t rl = t / (2 * cfg.c), slot = (t / 2) % cfg.c; const bool rev = (t & 1) == 0;
+	const uint32_t r = cfg.r0 + rl;
+	const uint32_t id = cand_refs[(uint64_t)r * cfg.c + slot];
+	const uint64_t ewb = A.word_off[r];
+	const uint32_t rlen = R.lens[id]; const uint64_t rwb = R.word_off[id];
+	uint32_t* out = anch + 3 * a;
+	uint32_t from = 0, skip = 0xffffffffu;                              // the scan of the next element starts at pair `from` and passes over read position `skip`
+	uint32_t run = 0, start_e = 0, start_r = 0, prev_e = 0, prev_r = 0, n_anch = 0;
+	for (uint32_t i = 0; i < (uint32_t)out_len; )
+	{
+		const uint32_t cnt = min(64u, (uint32_t)out_len - i);
+		const bool valid = lane < cnt;
+		uint32_t idx = 0, pe = 0, pr = 0; uint64_t mm = 0;
+		if (valid)
+		{
+			idx = (uint32_t)F[i + lane];
+			const uint64_t pw = P[idx];
+			pr = ~(uint32_t)pw & pr_mask; pe = (uint32_t)(pw >> cfg.pr) & pe_mask;
+			const uint64_t mraw = mmer_at(R, rwb, rev ? rlen - m - pr : pr, m);
+			mm = rev ? revcomp_m(mraw, m) : mraw;
+		}
+		const uint32_t idx_b = (uint32_t)__shfl_up((int)idx, 1, 64), pe_b = (uint32_t)__shfl_up((int)pe, 1, 64);
+		const uint32_t st = lane == 0 ? from : idx_b + 1, sk = lane == 0 ? skip : pe_b;
+		bool fail = false;
+		if (valid)
+		{
+			fail = idx < st || idx - st > LIS_WAVE_GAP || mmer_at(A, ewb, pe, m) != mm;
+			for (uint32_t j = st; !fail && j < idx; ++j)                // (at most LIS_WAVE_GAP turns)
+			{
+				const uint32_t ej = enc_pos(j);
+				fail = ej != sk && ej != pe && mmer_at(A, ewb, ej, m) == mm;
+			}
+		}
+		const uint64_t fb = __ballot(valid && fail);
+		const uint32_t f = fb ? (uint32_t)__builtin_ctzll(fb) : cnt;
+		uint32_t g = f;                                                 // elements settled in this step
+		if (f < cnt)
+		{
+			const uint64_t mmf = shfl_u64(mm, f);
+			const uint32_t stf = (uint32_t)__shfl((int)st, (int)f, 64), skf = (uint32_t)__shfl((int)sk, (int)f, 64);
+			uint32_t q = 0, jq = 0; bool found = false;
+			for (uint32_t j0 = stf; j0 < n && !found; j0 += 64)         // bounded by the list, as the lane form's ep < n
+			{
+				const uint32_t j = j0 + lane; uint32_t ej = 0; bool hit = false;
+				if (j < n) { ej = enc_pos(j); hit = ej != skf && mmer_at(A, ewb, ej, m) == mmf; }
+				const uint64_t hb = __ballot(hit);
+				if (hb) { const int hl = __builtin_ctzll(hb); q = (uint32_t)__shfl((int)ej, hl, 64); jq = j0 + (uint32_t)hl; found = true; }
+			}
+			if (!found) { q = enc_pos(n - 1); jq = n - 1; }             // (the scan always hits before the end)
+			if (lane == f) pe = q;
+			g = f + 1; from = jq + 1; skip = q;
+		}
+		else { from = (uint32_t)__shfl((int)idx, (int)cnt - 1, 64) + 1; skip = (uint32_t)__shfl((int)pe, (int)cnt - 1, 64); }
+		// merge: run heads by ballot, the anchors of the runs that end in this step in order
+		const uint32_t pe_p = (uint32_t)__shfl_up((int)pe, 1, 64), pr_p = (uint32_t)__shfl_up((int)pr, 1, 64);
+		const bool goes_on = lane == 0 ? (run && prev_e == pe - 1 && prev_r == pr - 1) : (pe_p == pe - 1 && pr_p == pr - 1);
+		const bool head = lane < g && !goes_on;
+		const uint64_t hb = __ballot(head);
+		if (hb)
+		{
+			const uint32_t h0 = (uint32_t)__builtin_ctzll(hb), hl = 63u - (uint32_t)__builtin_clzll(hb);
+			const uint32_t base = n_anch + (run ? 1u : 0u);
+			if (run && lane == 0) { out[3 * n_anch] = run + h0 + m - 1; out[3 * n_anch + 1] = start_e; out[3 * n_anch + 2] = start_r; }
+			const uint64_t later = hb & ~((2ULL << lane) - 1);
+			if (head && later)
+			{
+				const uint32_t w = base + (uint32_t)__popcll(hb & ((1ULL << lane) - 1));
+				out[3 * w] = (uint32_t)__builtin_ctzll(later) - lane + m - 1; out[3 * w + 1] = pe; out[3 * w + 2] = pr;
+			}
+			n_anch = base + (uint32_t)__popcll(hb) - 1;
+			run = g - hl; start_e = (uint32_t)__shfl((int)pe, (int)hl, 64); start_r = (uint32_t)__shfl((int)pr, (int)hl, 64);
+		}
+		else run += g;
+		prev_e = (uint32_t)__shfl((int)pe, (int)g - 1, 64); prev_r = (uint32_t)__shfl((int)pr, (int)g - 1, 64);
+		i += g;
+	}
+	if (lane == 0)
+	{
+		if (run) { out[3 * n_anch] = run + m - 1; out[3 * n_anch + 1] = start_e; out[3 * n_anch + 2] = start_r; ++n_anch; }
+		t_nanch[t] = n_anch; t_tot[t] = (uint32_t)out_len + n_anch * (m - 1);      // every chain element is in one run
+	}
 }
 
 // ---- A5': HiFi k-mer anchors (a9): AnalyseRefReadWithKmers / KmerBasedAnchors (encoder.cpp:870-1013,1113-1147) ------
@@ -935,6 +1159,12 @@ extern "C" cl_status cl_anchor_candidates_hifi(cl_ctx* ctx, const cl_reads* read
 	// reads above 1.5 x this many m-mers are matched segment by segment (k_match); COLORD_HIP_MATCH_SEG=0: one block per read whatever its length
 	const uint32_t match_seg = getenv("COLORD_HIP_MATCH_SEG") ? (uint32_t)std::max(0, atoi(getenv("COLORD_HIP_MATCH_SEG"))) : 16384u;
 	const uint32_t lds_dbg = getenv("COLORD_HIP_LDS_DBG") ? (uint32_t)atoi(getenv("COLORD_HIP_LDS_DBG")) : 0u;
+	// tasks of at least this many pairs are chained by a wave (k_lis_anchors_wave), the others by a lane; COLORD_HIP_LIS_WAVE_MIN=0: a lane for
+	// every task, 1: a wave for every non-empty task
+	const uint32_t lis_wave_min = getenv("COLORD_HIP_LIS_WAVE_MIN") ? (uint32_t)std::max(0, atoi(getenv("COLORD_HIP_LIS_WAVE_MIN"))) : LIS_WAVE_MIN_DEFAULT;
+	const uint32_t lis_dbg = getenv("COLORD_HIP_LIS_DBG") ? (uint32_t)atoi(getenv("COLORD_HIP_LIS_DBG")) : 0u;
+	DEV_ALLOC(ctx, X->lis_counts_d, (uint64_t)LIS_COUNT_LINES * 8);
+	HIP_TRY(ctx, hipMemsetAsync(X->lis_counts_d.p, 0, (uint64_t)LIS_COUNT_LINES * 64, ctx->stream));
 	auto prepare = [&](uint32_t r0, std::unique_ptr<TableBatch>& out) -> cl_status {
 		out = std::make_unique<TableBatch>();
 		TableBatch& B = *out;
@@ -1030,8 +1260,12 @@ extern "C" cl_status cl_anchor_candidates_hifi(cl_ctx* ctx, const cl_reads* read
 			CL_TRY(dev_sort_pairs(ctx, pairs.p, nullptr, n_pairs, 0, cfg.pe + cfg.pr + tb));
 		}
 		LAUNCH(ctx, k_task_pairs, grid_for((uint64_t)n_tasks + 1, 256), 256, (const uint64_t*)pairs.p, n_pairs, A, cfg, (const uint32_t*)n_distinct.p, n_tasks, pair_off.p, pair_cnt.p);
+			// both forms run over all tasks and each leaves at once for the tasks of the other: no count comes back to the host in between
 		LAUNCHB(ctx, n_pairs * 32.0, k_lis_anchors, grid_for(n_tasks, 64), 64, A, R, cfg, d_cand_refs, n_tasks, (const uint64_t*)pair_off.p, (const uint32_t*)pair_cnt.p, (const uint64_t*)pairs.p,
-			tf.p, ts.p, pred.p, anch.p, t_nanch.p, t_tot.p, (uint32_t)(getenv("COLORD_HIP_LIS_DBG") ? atoi(getenv("COLORD_HIP_LIS_DBG")) : 0));
+			tf.p, ts.p, pred.p, anch.p, t_nanch.p, t_tot.p, lis_wave_min, X->lis_counts_d.p, lis_dbg);
+		if (lis_wave_min)
+			LAUNCH(ctx, k_lis_anchors_wave, grid_for(n_tasks, LIS_WAVE_BLOCK / 64), LIS_WAVE_BLOCK, A, R, cfg, d_cand_refs, n_tasks, (const uint64_t*)pair_off.p, (const uint32_t*)pair_cnt.p, (const uint64_t*)pairs.p,
+				tf.p, ts.p, pred.p, anch.p, t_nanch.p, t_tot.p, lis_wave_min, X->lis_counts_d.p, lis_dbg);
 		HIP_TRY(ctx, hipGetLastError());
 		const uint64_t n_slots = (uint64_t)nb * c;
 		// HiFi: k-mer anchors from the shared k-mers of every (read, candidate)
@@ -1078,13 +1312,22 @@ extern "C" cl_status cl_anchor_candidates_hifi(cl_ctx* ctx, const cl_reads* read
 		o += chunk_n[i];
 	}
 	HIP_TRY(ctx, hipMemcpyAsync(X->cand_off.p + (uint64_t)nr * c, &total_anchors, 8, hipMemcpyHostToDevice, ctx->stream));
+	LAUNCH(ctx, k_lis_counts_sum, 1, 64, X->lis_counts_d.p);
+	HIP_TRY(ctx, hipMemcpyAsync(X->lis_counts, X->lis_counts_d.p, 48, hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	if (getenv("COLORD_HIP_ANCHOR_DEBUG"))
+		fprintf(stderr, "[anchors] chained by a wave: %llu tasks %llu pairs (%llu did not extend); by a lane: %llu tasks %llu pairs; longest list %llu; threshold %u\n",
+			X->lis_counts[0], X->lis_counts[1], X->lis_counts[4], X->lis_counts[2], X->lis_counts[3], X->lis_counts[5], lis_wave_min);
 	cl_timing_collect(ctx);
 	*out = guard.release();
 	return CL_OK;
 }
 extern "C" void cl_anchors_free(cl_anchors* a) { delete a; }
 extern "C" uint64_t cl_anchors_total(const cl_anchors* a) { return a->n_anchors; }
+extern "C" uint64_t cl_anchors_wave_tasks(const cl_anchors* a) { return a->lis_counts[0]; }
+extern "C" uint64_t cl_anchors_wave_pairs(const cl_anchors* a) { return a->lis_counts[1]; }
+extern "C" uint64_t cl_anchors_lane_tasks(const cl_anchors* a) { return a->lis_counts[2]; }
+extern "C" uint64_t cl_anchors_lane_pairs(const cl_anchors* a) { return a->lis_counts[3]; }
 extern "C" const uint32_t* cl_anchors_n_cands(const cl_anchors* a) { return a->n_cands.p; }
 extern "C" const uint32_t* cl_anchors_cands(const cl_anchors* a) { return a->cand.p; }
 extern "C" const uint64_t* cl_anchors_cand_offsets(const cl_anchors* a) { return a->cand_off.p; }

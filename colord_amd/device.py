@@ -907,6 +907,12 @@ class Anchors(_Obj):
 
     @property
     def total(self): return self.ctx.lib.cl_anchors_total(self.h)
+
+    def lis_counts(self):
+        """(tasks, pairs) chained by a wave and (tasks, pairs) chained by a lane, non-empty tasks only."""
+        lib = self.ctx.lib
+        return ((lib.cl_anchors_wave_tasks(self.h), lib.cl_anchors_wave_pairs(self.h)), (lib.cl_anchors_lane_tasks(self.h), lib.cl_anchors_lane_pairs(self.h)))
+
     def n_cands(self): return self._arr("cl_anchors_n_cands", self.n_reads, torch.int32)
     def cands(self): return self._arr("cl_anchors_cands", self.n_reads * self.c * 4, torch.int32).view(self.n_reads, self.c, 4)
     def cand_offsets(self): return self._arr("cl_anchors_cand_offsets", self.n_reads * self.c + 1, torch.int64)

@@ -287,6 +287,12 @@ cl_status cl_anchor_candidates_hifi(cl_ctx* ctx, const cl_reads* reads, const cl
                                     cl_anchors** out);
 void cl_anchors_free(cl_anchors* a);
 uint64_t cl_anchors_total(const cl_anchors* a);
+/* how the call chained its (read, candidate, orientation) tasks: non-empty tasks and their match pairs that went through the
+   wave form (tasks of at least COLORD_HIP_LIS_WAVE_MIN pairs) and through the lane form; counted on the device */
+uint64_t cl_anchors_wave_tasks(const cl_anchors* a);
+uint64_t cl_anchors_wave_pairs(const cl_anchors* a);
+uint64_t cl_anchors_lane_tasks(const cl_anchors* a);
+uint64_t cl_anchors_lane_pairs(const cl_anchors* a);
 const uint32_t* cl_anchors_n_cands(const cl_anchors* a);        /* device, n_reads */
 const uint32_t* cl_anchors_cands(const cl_anchors* a);          /* device, n_reads*c*4: ref_id, rev, tot_anchor_len, n_anchors */
 const uint64_t* cl_anchors_cand_offsets(const cl_anchors* a);   /* device, n_reads*c+1: first anchor of each slot */
