@@ -68,6 +68,15 @@ class Edits(C.Structure):
     as_dict = Report.as_dict
 
 
+KSPEC_EXACT = 4096
+class KSpec(C.Structure):
+    """cl_kspec: the k-mer count spectrum; every field adds over disjoint key ranges except max_count (max)."""
+    _fields_ = [("kmers", C.c_uint64), ("distinct", C.c_uint64), ("max_count", C.c_uint64), ("exact", C.c_uint64 * KSPEC_EXACT),
+                ("big", C.c_uint64 * 33), ("big_mass", C.c_uint64 * 33)]
+
+    as_dict = Report.as_dict
+
+
 _P = C.c_void_p
 class CompressParams(C.Structure):
     _fields_ = [("k", C.c_uint32), ("f", C.c_uint32), ("ci", C.c_uint32), ("cs", C.c_uint32), ("c", C.c_uint32),
@@ -134,6 +143,12 @@ _SIG = {
     "cl_ctx_set_edit_profile": (None, [_P, C.c_int]),
     "cl_ctx_edit_profile": (C.c_int32, [_P, C.POINTER(Edits)]),
     "cl_compressor_edit_profile": (C.c_int32, [_P, C.POINTER(Edits)]),
+    "cl_kspec_clear": (None, [C.POINTER(KSpec)]),
+    "cl_kspec_add": (None, [C.POINTER(KSpec), C.POINTER(KSpec)]),
+    "cl_kmer_spectrum_heads": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(KSpec)]),
+    "cl_ctx_set_kmer_spectrum": (None, [_P, C.c_int]),
+    "cl_ctx_kmer_spectrum": (C.c_int32, [_P, C.POINTER(KSpec)]),
+    "cl_compressor_kmer_spectrum": (C.c_int32, [_P, C.POINTER(KSpec)]),
     "cl_digest_bases": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(Digest)]),
     "cl_digest_quals": (C.c_int32, [_P, C.POINTER(QualParams), _P, _P, _P, C.c_uint64, C.POINTER(Digest)]),
     "cl_digest_bases_host": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(Digest)]),

@@ -120,6 +120,7 @@ extern "C" void cl_ctx_destroy(cl_ctx* c)
 	if (c->slots_h) (void)hipHostFree(c->slots_h);
 	delete c->report_acc;
 	delete c->edits_acc;
+	delete c->kspec_acc;
 	const int dev = c->device;
 	delete c;
 	cl_device_pool_release(dev);

@@ -204,6 +204,7 @@ int run_compress(int argc, char** argv)
 	check_report_options(O, with_qual);
 	if (O.report) cl_ctx_set_report(ctx, 1);
 	if (O.edit_profile) cl_ctx_set_edit_profile(ctx, 1);
+	if (O.kmer_spectrum) cl_ctx_set_kmer_spectrum(ctx, 1);
 	std::vector<uint64_t> report_lens;                          // --report: every read length, as the reader hands the reads over in pass 1 (N50 / N90)
 	ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, nullptr, estimated_bases(R), &cmp), "cl_compressor_create");
 	if (O.qual_domain_symbols)
@@ -343,6 +344,12 @@ int run_compress(int argc, char** argv)
 		EditsSet E;
 		ck(ctx, cl_compressor_edit_profile(cmp, E.e.get()), "cl_compressor_edit_profile");
 		add_edits(ar, E, n, total);
+	}
+	if (O.kmer_spectrum)
+	{
+		KSpecSet K;
+		ck(ctx, cl_compressor_kmer_spectrum(cmp, K.s.get()), "cl_compressor_kmer_spectrum");
+		add_kspec(ar, K, prm.cp, GM.on, 1, ks.tot_kmers, ks.n_unique);
 	}
 	if (O.qual_domain_symbols)
 	{

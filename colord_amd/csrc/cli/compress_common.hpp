@@ -9,6 +9,7 @@
 #include "digest_stream.hpp"
 #include "report_stream.hpp"
 #include "edits_stream.hpp"
+#include "kspec_stream.hpp"
 #include <ctime>
 #include <mutex>
 
@@ -329,6 +330,15 @@ inline void add_edits(ArchiveWriter& ar, const EditsSet& S, uint64_t n_reads, ui
 	if (S.e->reads != n_reads || S.e->bases != n_bases) die("internal: the edit profile did not see every read");
 	const std::vector<uint8_t> b = S.pack();
 	ar.add(ar.reg("hipedits"), b.data(), b.size(), 0);
+}
+// --kmer-spectrum: the `hipkmers` stream (kspec_stream.hpp), before finish_archive: what the compressors' contexts counted of the k-mers of pass 1,
+// `sets` independent sets added; it must be every k-mer the counters reported
+inline void add_kspec(ArchiveWriter& ar, KSpecSet& S, const cl_compress_params& cp, bool genome, uint32_t sets, uint64_t tot_kmers, uint64_t n_unique)
+{
+	if (S.s->kmers != tot_kmers || S.s->distinct != n_unique) die("internal: the k-mer spectrum did not see every k-mer");
+	S.flags = genome ? 1u : 0u; S.k = cp.k; S.f = cp.f; S.ci = cp.ci; S.cs = cp.cs; S.sets = sets;
+	const std::vector<uint8_t> b = S.pack();
+	ar.add(ar.reg("hipkmers"), b.data(), b.size(), 0);
 }
 // --report with a *-fix mode: the -D values must be qualities the report can index
 inline void check_report_options(const Options& O, bool with_qual)

@@ -20,6 +20,7 @@ struct RankOut {
 	uint64_t n_reads = 0, mean_read_len = 0; uint32_t sparse_range = 0, n_refs = 0; cl_kmer_stats ks{};
 	uint64_t dna_base = 0, qual_base = 0, qual_framed = 0;     // where its framed `dna` / `qual` parts start in the file; bytes of the latter
 	uint64_t moved = 0;
+	std::unique_ptr<cl_kspec> kspec;                           // --kmer-spectrum: what this rank's context counted of the key range it owns (of its own k-mers: an independent domain)
 	std::unique_ptr<cl_edits> edits;                           // --edit-profile: what this rank's compressor and its lanes counted of their tuple streams
 	std::unique_ptr<cl_report> report;                         // --report: what this rank's compressor counted of its reads
 	cl_digest dig[3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } }, dig_all[3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } };      // --digest: dna / qual / (--digest-values) qual-values of this rank's reads; of all ranks (as gathered with the byte counts)
@@ -120,6 +121,7 @@ int run_compress_multi(const Options& O)
 		if (O.digest && !independent) cl_ctx_set_digest(ctx, 1);
 		if (digest_values && !independent) cl_ctx_set_digest_values(ctx, 1);
 		if (O.edit_profile) cl_ctx_set_edit_profile(ctx, 1);
+		if (O.kmer_spectrum) cl_ctx_set_kmer_spectrum(ctx, 1);
 		if (O.report) cl_ctx_set_report(ctx, 1);                            // (the report has no read indices: a rank's and an independent domain's compressor count alike)
 		ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, T ? &X : nullptr, my_bases, &cmp), "cl_compressor_create");
 		if (GM.on) GM.count_kmers(ctx, cmp);
@@ -164,6 +166,7 @@ int run_compress_multi(const Options& O)
 		auto reload = [&](size_t ci) { host.clear(); fill(cut[ci], cut[ci + 1]); up.upload(ctx, host, chunks[ci]); };
 		if (!O.stream_input) host.release();
 		ck(ctx, cl_compressor_count_finish(cmp, &RO.ks), "k-mer counting (exchange 1)");
+		if (O.kmer_spectrum) { RO.kspec.reset(new cl_kspec); ck(ctx, cl_compressor_kmer_spectrum(cmp, RO.kspec.get()), "cl_compressor_kmer_spectrum"); }
 		if (GM.on) GM.add_pseudo_reads(ctx, cmp, ka.k);
 		for (size_t ci = 0; ci < chunks.size(); ++ci)
 		{
@@ -307,6 +310,12 @@ int run_compress_multi(const Options& O)
 		EditsSet E;
 		for (uint32_t r = 0; r < world; ++r) if (out[r].edits) ed_add(E.e.get(), out[r].edits.get());
 		add_edits(ar, E, n, total);
+	}
+	if (O.kmer_spectrum)
+	{	// ranks own disjoint key ranges of ONE k-mer set (their counters return the sums of all ranks); independent domains are a set each
+		KSpecSet K; uint64_t tot_kmers = out[0].ks.tot_kmers, n_unique = out[0].ks.n_unique;
+		for (uint32_t r = 0; r < world; ++r) { if (out[r].kspec) ks_add(K.s.get(), out[r].kspec.get()); if (independent && r) { tot_kmers += out[r].ks.tot_kmers; n_unique += out[r].ks.n_unique; } }
+		add_kspec(ar, K, prm.cp, GM.on, independent ? world : 1, tot_kmers, n_unique);
 	}
 	finish_archive(ar, O, R, tot);
 	if (use_rccl) rccl.destroy_all();

@@ -5,6 +5,7 @@
 // against it while it is decoded; `check` decodes without writing and prints the digests.
 #include "reader.hpp"
 #include "edits_stream.hpp"
+#include "kspec_stream.hpp"
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <ctime>
@@ -108,9 +109,14 @@ struct DeviceQualDecoder {
 
 int run_info(int argc, char** argv)
 {
-	bool want_report = false, want_edits = false, json = false; std::vector<std::string> pos;
-	for (int i = 2; i < argc; ++i) { const std::string a = argv[i]; if (a == "--report") want_report = true; else if (a == "--edit-profile") want_edits = true; else if (a == "--json") json = true; else pos.push_back(a); }
-	if (pos.size() != 1 || (json && !want_report && !want_edits) || (want_report && want_edits)) { fprintf(stderr, "usage: colord_hip info [--report [--json]] [--edit-profile [--json]] archive.colord\n"); return 1; }
+	bool want_report = false, want_edits = false, want_kspec = false, json = false; std::vector<std::string> pos;
+	for (int i = 2; i < argc; ++i)
+	{
+		const std::string a = argv[i];
+		if (a == "--report") want_report = true; else if (a == "--edit-profile") want_edits = true; else if (a == "--kmer-spectrum") want_kspec = true; else if (a == "--json") json = true; else pos.push_back(a);
+	}
+	const int wanted = (want_report ? 1 : 0) + (want_edits ? 1 : 0) + (want_kspec ? 1 : 0);
+	if (pos.size() != 1 || (json && !wanted) || wanted > 1) { fprintf(stderr, "usage: colord_hip info [--report [--json]] [--edit-profile [--json]] [--kmer-spectrum [--json]] archive.colord\n"); return 1; }
 	const std::string& path = pos[0];
 	ArchiveReader ar;
 	if (!ar.open(path)) die("cannot open archive: " + path);
@@ -130,6 +136,15 @@ int run_info(int argc, char** argv)
 		if (have == 0) die("no edit profile is stored in this archive (written without --edit-profile)");
 		if (have < 0) die("the archive's `hipedits` stream is not one this build reads");
 		if (json) print_edits_json(stdout, E); else print_edits(stdout, E);
+		return 0;
+	}
+	if (want_kspec)
+	{	// the stored k-mer count spectrum alone, on stdout: nothing is decoded
+		ar.close();
+		KSpecSet K; const int have = read_hipkmers(path, K);
+		if (have == 0) die("no k-mer spectrum is stored in this archive (written without --kmer-spectrum)");
+		if (have < 0) die("the archive's `hipkmers` stream is not one this build reads");
+		if (json) print_kspec_json(stdout, K); else print_kspec(stdout, K);
 		return 0;
 	}
 	std::vector<uint8_t> b; uint64_t meta = 0;
@@ -152,6 +167,11 @@ int run_info(int argc, char** argv)
 		fprintf(stderr, "edit profile: %llu of %llu reads coded with an edit script, %llu aligned bases (`colord_hip info --edit-profile [--json]` prints it)\n", (unsigned long long)eds.e->kind_reads[2], (unsigned long long)eds.e->reads,
 			(unsigned long long)edits_derived(*eds.e).aligned);
 	else if (have < 0) fprintf(stderr, "edit profile: a `hipedits` stream this build cannot read\n");
+	KSpecSet ksp;
+	if (const int have = read_hipkmers(path, ksp); have > 0)
+		fprintf(stderr, "k-mer spectrum: %llu sampled k-mers (1 in %u), %llu distinct, highest count %llu (`colord_hip info --kmer-spectrum [--json]` prints it)\n", (unsigned long long)ksp.s->kmers, ksp.f, (unsigned long long)ksp.s->distinct,
+			(unsigned long long)ksp.s->max_count);
+	else if (have < 0) fprintf(stderr, "k-mer spectrum: a `hipkmers` stream this build cannot read\n");
 	return 0;
 }
 

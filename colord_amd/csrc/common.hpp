@@ -355,6 +355,8 @@ struct cl_ctx {
 	bool edit_profile = false;                   // cl_ctx_set_edit_profile: tuple_streams (pass_steps.hpp) adds the edit-operation profile of every batch it makes (edits.hip)
 	cl_edits* edits_acc = nullptr;               // the total of the batches made on THIS context (under edits_mu: cl_ctx_edit_profile reads the encode lanes' from the owner's thread); freed with the context
 	mutable std::mutex edits_mu;
+	bool kmer_spectrum = false;                  // cl_ctx_set_kmer_spectrum: count_range (kmer.hip) adds the count spectrum of every key range it counts (kspec.hip)
+	cl_kspec* kspec_acc = nullptr;               // the total so far (owner thread only); freed with the context
 	uint64_t gap_paths[11] = { 0 };              // cl_ctx_gap_paths: the last cl_encode_reads' gaps per size class 0..7, quad -> wave, giant -> wave, wave-pool redo rounds (owner thread only)
 	std::map<std::string, KernelTime> times;     // per-kernel accumulated HIP-event time of the last API call
 	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;

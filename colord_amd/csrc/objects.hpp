@@ -66,6 +66,8 @@ cl_status digest_values_chunk(cl_ctx* ctx, const cl_reads* reads, const cl_qual_
 cl_status report_chunk(cl_ctx* ctx, const cl_reads* reads, const cl_qual_params* qparams, const uint8_t* d_quals, const uint64_t* d_base_off);
 // edits.hip (cl_ctx_set_edit_profile): the edit-operation profile of a batch of tuple streams, added to the total of the context that made them
 cl_status edit_profile_chunk(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads);
+// kspec.hip (cl_ctx_set_kmer_spectrum): the count spectrum of one counted key range — the run starts of its n sorted keys — added to the context's total
+cl_status kmer_spectrum_range(cl_ctx* ctx, const uint32_t* d_head_pos, uint64_t n_heads, uint64_t n);
 const cl_qual_params* cl_qual_coder_params(const cl_qual_coder* q);     // qual.hip: the parameters the coder was created with
 
 // the DNA coder's state-independent half ahead of time (dna.hip): lookahead.hip walks the NEXT chunk's tuples from the hook that

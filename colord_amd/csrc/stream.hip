@@ -446,6 +446,10 @@ extern "C" cl_status cl_compressor_edit_profile(const cl_compressor* c, cl_edits
 {
 	return c ? cl_ctx_edit_profile(c->ctx, out) : CL_E_INVALID;
 }
+extern "C" cl_status cl_compressor_kmer_spectrum(const cl_compressor* c, cl_kspec* out)
+{
+	return c ? cl_ctx_kmer_spectrum(c->ctx, out) : CL_E_INVALID;
+}
 extern "C" cl_status cl_compressor_verified_streams(const cl_compressor* c, uint64_t* parts, uint64_t* symbols, uint64_t* bytes)
 {
 	if (!c) return CL_E_INVALID;

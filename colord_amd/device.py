@@ -56,7 +56,8 @@ class _OrderedLib:
                   "cl_ctx_set_digest_values", "cl_ctx_digest_values", "cl_compressor_digest_values", "cl_qual_values_host", "cl_digest_qual_values_host",
                   "cl_qual_coder_domains", "cl_compressor_qual_domains", "cl_ctx_gap_paths",
                   "cl_report_clear", "cl_report_add", "cl_report_bases_host", "cl_report_quals_host", "cl_report_values_host", "cl_ctx_set_report", "cl_ctx_report", "cl_compressor_report",
-                  "cl_edits_clear", "cl_edits_add", "cl_edit_profile_host", "cl_edit_profile_error", "cl_ctx_set_edit_profile", "cl_ctx_edit_profile", "cl_compressor_edit_profile")
+                  "cl_edits_clear", "cl_edits_add", "cl_edit_profile_host", "cl_edit_profile_error", "cl_ctx_set_edit_profile", "cl_ctx_edit_profile", "cl_compressor_edit_profile",
+                  "cl_kspec_clear", "cl_kspec_add", "cl_ctx_set_kmer_spectrum", "cl_ctx_kmer_spectrum", "cl_compressor_kmer_spectrum")
 
     def __init__(self, lib, device):
         self._lib, self._device, self._cache = lib, device, {}
@@ -213,6 +214,28 @@ class Context:
             self.lib.cl_edits_clear(C.byref(acc))
         n = max(es_off.numel() - 1, 0)
         _check(self, self.lib.cl_edit_profile(self.h, refs.h, es.data_ptr() if es.numel() else None, es_off.data_ptr() if n else None, n, flush_bytes, max_blocks, C.byref(acc)))
+        return acc
+
+    def set_kmer_spectrum(self, on: bool = True):
+        """cl_ctx_set_kmer_spectrum: every count_filter() on this context, and the pass 1 of its compressors, adds the count spectrum of the
+        k-mers it counted, before the cut at ci and the saturation at cs (cleared when switched on)."""
+        self.lib.cl_ctx_set_kmer_spectrum(self.h, int(bool(on)))
+
+    def kmer_spectrum(self) -> dict:
+        """cl_ctx_kmer_spectrum: the spectrum so far on this context, as ints and numpy uint64 arrays (N.KSpec's fields)."""
+        s = N.KSpec()
+        _check(None, self.lib.cl_ctx_kmer_spectrum(self.h, C.byref(s)))
+        return s.as_dict()
+
+    def kmer_spectrum_heads(self, head_pos: torch.Tensor, n: int, max_blocks: int = 0, acc: "N.KSpec | None" = None) -> "N.KSpec":
+        """cl_kmer_spectrum_heads: the spectrum of the runs that start at the ascending positions head_pos (uint32 values, in a 4-byte dtype) of
+        a sorted array of n keys, added to acc.  Malformed positions raise (CL_E_INVALID) and leave acc as it is."""
+        assert head_pos.element_size() == 4
+        head_pos = head_pos.contiguous()
+        if acc is None:
+            acc = N.KSpec()
+            self.lib.cl_kspec_clear(C.byref(acc))
+        _check(self, self.lib.cl_kmer_spectrum_heads(self.h, head_pos.data_ptr() if head_pos.numel() else None, head_pos.numel(), n, max_blocks, C.byref(acc)))
         return acc
 
     @staticmethod

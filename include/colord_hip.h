@@ -479,6 +479,37 @@ const char* cl_edit_profile_error(uint32_t code);
 void cl_ctx_set_edit_profile(cl_ctx* ctx, int on);
 cl_status cl_ctx_edit_profile(const cl_ctx* ctx, cl_edits* out);
 
+/* ---- k-mer count spectrum (no counterpart in the reference) — what the k-mer stage saw -------------------------------- */
+/* How many distinct sampled k-mers occur once, twice, and so on: the run lengths of the sorted keys of cl_kmer_count_filter, BEFORE
+ * the cut at ci and the saturation at cs.  The k-mers are the 1-in-f hash sample of cl_kmer_scan, so every number is of the sample.
+ * Every field is unsigned 64-bit and adds over disjoint key ranges, in any order, except max_count, which combines by max.
+ *   kmers        occurrences counted: the sum of c over all distinct k-mers (= cl_kmer_stats.tot_kmers)
+ *   distinct     distinct k-mers (= cl_kmer_stats.n_unique)
+ *   max_count    the largest c
+ *   exact[c]     distinct k-mers that occur exactly c times, 1 <= c <= 4095; exact[0] stays 0
+ *   big[b], big_mass[b]   k-mers with c >= 4096 by the bit length b of c (13..32): how many, and the sum of their c */
+#define CL_KSPEC_EXACT 4096
+typedef struct cl_kspec {
+	uint64_t kmers, distinct, max_count;
+	uint64_t exact[CL_KSPEC_EXACT];
+	uint64_t big[33], big_mass[33];
+} cl_kspec;
+void cl_kspec_clear(cl_kspec* s);
+void cl_kspec_add(cl_kspec* dst, const cl_kspec* src);
+/* The spectrum of the runs of a sorted key array of n keys (n < 2^32), added to *acc (host): d_head_pos[0 .. n_heads) holds the
+ * ascending start positions of the runs, run j has (j + 1 < n_heads ? d_head_pos[j + 1] : n) - d_head_pos[j] keys.  On the device
+ * (k_run_spectrum): persistent blocks of 256 lanes count into 32-bit cells in LDS, the values 1..8 per wave by ballot, and add the
+ * non-zero cells to a 64-bit scratch total at their end; max_blocks bounds the grid (0: the default, four per CU) and changes no
+ * result.  Positions that are not strictly ascending or not below n, n_heads > n and n >= 2^32 are CL_E_INVALID and NOTHING is
+ * added; they never make the kernel read or count out of range.  n_heads == 0 is CL_OK and adds nothing. */
+cl_status cl_kmer_spectrum_heads(cl_ctx* ctx, const uint32_t* d_head_pos, uint64_t n_heads, uint64_t n, uint32_t max_blocks, cl_kspec* acc);
+/* Opt-in (off by default: one flag test per counted key range, no launch, no allocation, every output the same).  While it is on,
+ * every cl_kmer_count_filter on this context — the one-sort path and every key range above the count limit; in a multi-GPU run a
+ * rank's own key range — adds the spectrum of what it counted.  cl_ctx_kmer_spectrum: the total so far (cleared when the flag is
+ * switched on). */
+void cl_ctx_set_kmer_spectrum(cl_ctx* ctx, int on);
+cl_status cl_ctx_kmer_spectrum(const cl_ctx* ctx, cl_kspec* out);
+
 /* ---- a14 + a16: CDNACoder / CEntrComprReads (dna_coder.{h,cpp}, entr_read.h:56-80) --------------------- */
 typedef struct cl_dna_coder cl_dna_coder;
 /* CDNACoder::Init(true, maxCandidates, level, ., n_ref_genome_pseudo_reads): one adaptive model set that
@@ -641,6 +672,9 @@ cl_status cl_compressor_report(const cl_compressor* c, cl_report* out);
 /* cl_ctx_edit_profile of the compressor's context (cl_ctx_set_edit_profile): the profile of the chunks whose tuple streams are made,
  * its encode lanes' included — after the last cl_compressor_encode, of every chunk */
 cl_status cl_compressor_edit_profile(const cl_compressor* c, cl_edits* out);
+/* cl_ctx_kmer_spectrum of the compressor's context (cl_ctx_set_kmer_spectrum): after cl_compressor_count_finish, the spectrum of the
+ * k-mers pass 1 counted (a reference genome's included) */
+cl_status cl_compressor_kmer_spectrum(const cl_compressor* c, cl_kspec* out);
 
 /* cl_qual_coder_set_domain_symbols / cl_qual_coder_domains of the compressor's quality coder.  The setting must be made before the
  * first cl_compressor_encode or cl_compressor_prepare_parts call (CL_E_INVALID afterwards, and without a quality stream); the `dna`
