@@ -1,12 +1,18 @@
 // encode_es.hip — kernels and host driver of the edit-script encoder (a10 + a11 + a12); the algorithm, its data
 // model (frames, gaps, levels) and the reference citations are in encode_core.hpp.
 //
-// Per recursion level L (host loop, <= maxRecurence + 1 iterations, each a handful of launches over ALL level-L gaps):
-//   k_frame_gap_counts -> scan -> k_gap_geometry -> scans (script capacity, pending slots) -> sort gaps by size class
-//   -> k_align_small<NB> (one lane per gap, rows <= 64*NB, columns <= 256: Myers' recurrence in registers, sequences and
-//      the script in LDS, per-column history lane-interleaved in HBM) / k_align_large (the rest: lane pool, Hirschberg)
-//   -> k_gap_stats (estimator statistics or the static entropy decision) -> k_spawn_mark -> scans -> k_spawn_fill.
-// Then k_estimator (one lane per reader pack) and k_emit_tuples (one lane per read, count pass + write pass).
+// Per recursion level L (the loop of cl_encode_reads, <= maxRecurence + 1 iterations, each a handful of launches over ALL level-L gaps):
+//   main stream: k_frame_gap_counts -> scan -> k_gap_geometry -> scans (script capacity, pending slots) -> sort by (size class, size)
+//                -> k_class_bounds -> the class bounds on the host; then the aligners, side by side —
+//   side:   classes 1-4, k_align_small<NB>: one lane per gap, rows <= 64 NB, columns <= 256 (Myers' recurrence in registers, sequences
+//           and script in LDS, per-column history lane-interleaved in HBM)
+//   side2:  class 5, k_align_quad_rows: up to 16 row blocks, four gaps per wave, banded
+//   side3:  class 7, k_giant_stage / _level / _leaves / _finish: many waves per gap (align_giant.hpp)
+//   main:   class 6, k_align_wave: a wave per gap on a bump pool in HBM, in rounds of growing pools (the host reads each round's redo list);
+//           then the redo lists of class 5 and of class 7, read back in that order and run through the same rounds
+//   main stream, when classes 1-4 are through too: k_gap_stats[_long] (estimator statistics or the static entropy decision) ->
+//                k_gap_sums[_long] -> k_spawn_mark -> scans -> k_spawn_fill.
+// Then k_estimator (one wave per reader pack) and k_emit_count_wave / k_emit_write_wave (one wave per read; emit_wave.hpp), k_emit_plain.
 #include "objects.hpp"
 #include "encode_core.hpp"
 #include "align_wave.hpp"
@@ -14,10 +20,10 @@
 #include "align_giant.hpp"
 #include "emit_wave.hpp"
 #include <algorithm>
+#include <chrono>
+#include <climits>
 #include <memory>
 #include <vector>
-#include <thread>
-#include <chrono>
 
 struct cl_anchors;   // anchors.hip
 extern "C" const uint32_t* cl_anchors_n_cands(const cl_anchors* a);
@@ -755,22 +761,8 @@ __global__ __launch_bounds__(64) void k_align_quad_rows(const uint32_t* __restri
 	if (PROF && lane == 0) { atomicAdd(prof + 6, (unsigned long long)wstat.iters); atomicAdd(prof + 7, (unsigned long long)wstat.miss); atomicAdd(prof + 8, (unsigned long long)wstat.hit); }
 }
 
-// the rest: one lane per gap, lane pool in HBM; gaps whose lane ran out of pool are redone with larger pools
-__global__ __launch_bounds__(64) void k_align_large(const uint32_t* __restrict__ list, uint32_t n_list, GapRec* __restrict__ gaps, char* __restrict__ es_pool, ArenaV A, ArenaV R,
-                                                   uint8_t* __restrict__ scratch, uint64_t per_lane, unsigned int* __restrict__ next, uint32_t* __restrict__ redo, unsigned int* __restrict__ n_redo)
-{
-	LanePool pool{ scratch + (uint64_t)(blockIdx.x * blockDim.x + threadIdx.x) * per_lane, per_lane, 0, false, 0 };
-	for (;;)
-	{
-		const uint32_t slot = atomicAdd(next, 1u);
-		if (slot >= n_list) break;
-		const uint32_t gi = list[n_list - 1 - slot];                            // the list is ascending by size: largest first
-		pool.top = 0; pool.overflow = false; pool.why = 0;
-		GapRec g = gaps[gi];
-		if (!align_large_gap(pool, g, A, R, es_pool + g.es_off)) { redo[atomicAdd(n_redo, 1u)] = gi; continue; }
-		gaps[gi].es_len = g.es_len; gaps[gi].d_before = g.d_before;
-	}
-}
+// (no lane-per-gap kernel: align_large (align_dev.hpp) and align_large_gap (encode_core.hpp) stay as the reference that
+// tests/tools/encode_host.hip compiles for the host and the device aligners are compared with)
 
 // short gaps (the estimator decides them later): one lane per gap; long gaps are listed for k_gap_stats_long
 __global__ void k_gap_stats(LevelV L, ArenaV A, EncCfg cfg, const uint32_t* __restrict__ pend_idx, uint32_t* __restrict__ spawn_flag, uint32_t* __restrict__ long_list)
@@ -1073,6 +1065,366 @@ struct LevelBufs {
 	LevelV view() { return LevelV{ frames.p, cands.p, gaps.p, es.p, pend.p, dec.p, n_frames, n_gaps, sums.p }; }
 };
 } // namespace
+#include "encode_diag.hpp"
+
+// ---- the host driver: what a call knows, what a level knows, the steps of a level ---------------------------------------------------
+namespace {
+// Every environment switch of this file, read once at the entry of cl_encode_reads: per call, so a tool may set one between two calls
+struct EncKnobs {
+	uint32_t small_per_cu, quad_waves;   // tuning: blocks of k_align_small per CU (15 - 25 KB of LDS each), waves of k_align_quad_rows at most (18.5 KB each)
+	uint32_t wave_debug_stage;           // handed to k_align_wave
+	bool no_team_align;                  // the giant gaps go to the wave kernel (tools/giant_check.py's comparison)
+	bool gap_debug, gap_shapes, quad_profile, wave_profile, wave_heartbeat;   // the diagnostics of encode_diag.hpp
+	static EncKnobs read()
+	{
+		auto num = [](const char* name, int dflt, int least) { const char* e = getenv(name); return (uint32_t)(e ? std::max(least, atoi(e)) : dflt); };
+		auto on = [](const char* name) { return getenv(name) != nullptr; };
+		return EncKnobs{ num("COLORD_HIP_SMALL_PER_CU", 4, 1), num("COLORD_HIP_QUAD_WAVES", 2048, 64), num("COLORD_HIP_WAVE_DEBUG_STAGE", 0, INT_MIN), on("COLORD_HIP_NO_TEAM_ALIGN"),
+			on("COLORD_HIP_GAP_DEBUG"), on("COLORD_HIP_GAP_SHAPES"), on("COLORD_HIP_QUAD_PROFILE"), on("COLORD_HIP_WAVE_PROFILE"), on("COLORD_HIP_WAVE_HEARTBEAT") };
+	}
+};
+// the constants of one call.  st: the context's main stream; n_cu: the device's CUs (cl_ctx_create); err: device word, bit 2 = inconsistent anchors
+struct EncCall { cl_ctx* ctx; hipStream_t st; ArenaV A, R; AnchorsV AV; EncCfg cfg; const uint8_t* has_n; uint32_t nr, n_cu; uint32_t* err; EncKnobs knobs; };
+
+// The temporaries of one level that more than one step uses.  All of it lives to the end of the level's loop body: kernels of the main
+// stream still read these buffers when the step that launched them returns, and the side streams read ids.  The buffers go back to the
+// device pool, which the encode lanes share, in the reverse order of their declaration (profiles/encode_driver_ab.txt: keep that order).
+struct LevelWork {
+	DevBuf<uint32_t> first, capw, pflag, keys, ids; DevBuf<uint64_t> es_off; DevBuf<uint32_t> bounds;   // gaps: first of a frame; script capacity, "pending" flag (scanned), sort key, id by key; script offset; hb on the device
+	uint64_t ng = 0, es_total = 0, n_pend = 0;
+	LevelV V;                                          // the level's view, taken before L.sums exists (the kernels that need the sums get them as an argument)
+	uint32_t hb[N_CLASSES + 3] = { 0 };                // class c is ids[hb[c] .. hb[c + 1]); [N_CLASSES + 1], [+ 2]: the giants' summed and largest script capacity
+	unsigned long long h_cb[2 * N_CLASSES] = { 0 };    // bytes, then DP cells, per class (timing contexts only: 0 otherwise)
+	uint32_t count(uint32_t cls) const { return hb[cls + 1] - hb[cls]; }
+	const uint32_t* list(uint32_t cls) const { return ids.p + hb[cls]; }
+	double bytes(uint32_t cls) const { return 1.25 * (double)h_cb[cls]; }   // 2-bit symbols in, a script byte per symbol out
+	double cells(uint32_t cls) const { return (double)h_cb[N_CLASSES + cls]; }
+};
+// ... and those of its decisions and children (declared after the aligners' objects): spawn flag (scanned), its candidates, the two lists of long gaps, candidate offset
+struct SpawnWork { DevBuf<uint32_t> sflag, sncand, long_list, sum_long; DevBuf<uint64_t> cbase; };
+
+// Joins a side stream on every way out of its scope.  As the LAST member of an object it is destroyed FIRST: the object's buffers
+// outlive the kernels of the stream that use them, also when a step returns early with an error.
+struct StreamJoin {
+	hipStream_t s = nullptr;
+	~StreamJoin() { if (s) (void)hipStreamSynchronize(s); }
+	// waits for the stream (a host wait) and returns the second word of its aligner's two-word counter: the gaps it hands back
+	cl_status redo_count(cl_ctx* ctx, const unsigned int* cnt, uint32_t& n_redo)
+	{
+		unsigned int hc[2];
+		HIP_TRY(ctx, hipMemcpyAsync(hc, cnt, 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(ctx, hipStreamSynchronize(s));
+		s = nullptr;
+		n_redo = hc[1];
+		return CL_OK;
+	}
+};
+
+using Levels = std::vector<std::unique_ptr<LevelBufs>>;
+// level 0: one frame per read that has candidates.  Host waits (main stream): two scan totals, then the frames (flag / ncand / cbase go)
+cl_status level0_frames(const EncCall& E, uint32_t* frame_of_read, Levels& levels)
+{
+	cl_ctx* ctx = E.ctx; const uint32_t nr = E.nr;
+	auto L = std::make_unique<LevelBufs>();
+	DevBuf<uint32_t> flag, ncand; DEV_ALLOC(ctx, flag, (uint64_t)nr + 1); DEV_ALLOC(ctx, ncand, (uint64_t)nr + 1);
+	DevBuf<uint64_t> cbase; DEV_ALLOC(ctx, cbase, (uint64_t)nr + 1);
+	LAUNCH(ctx, k_read_flags, grid_for(nr, 256), 256, E.AV.n_cands, E.has_n, nr, flag.p, ncand.p);
+	uint64_t nf = 0;
+	CL_TRY(dev_exclusive_scan_u64(ctx, ncand.p, cbase.p, nr, &L->n_cands));
+	CL_TRY(dev_exclusive_scan_u32(ctx, flag.p, nr, &nf));
+	L->n_frames = (uint32_t)nf;
+	DEV_ALLOC(ctx, L->frames, nf + 1); DEV_ALLOC(ctx, L->cands, L->n_cands + 1);
+	LAUNCH(ctx, k_frames_level0, grid_for(nr, 256), 256, E.A, E.AV, E.cfg.c, E.has_n, nr, (const uint32_t*)flag.p, (const uint64_t*)cbase.p, L->frames.p, L->cands.p, frame_of_read);
+	HIP_TRY(ctx, hipGetLastError());
+	HIP_TRY(ctx, hipStreamSynchronize(E.st));
+	levels.push_back(std::move(L));
+	return CL_OK;
+}
+
+// the gaps of a level: counts -> scan -> geometry -> scans -> offsets, and the level's buffers as their sizes become known.
+// Host waits (main stream): the three scan totals — gaps, script symbols, pending slots — each of which sizes the next allocation
+cl_status level_gaps(const EncCall& E, LevelBufs& L, LevelWork& W)
+{
+	cl_ctx* ctx = E.ctx;
+	DEV_ALLOC(ctx, W.first, (uint64_t)L.n_frames + 1);
+	LAUNCH(ctx, k_frame_gap_counts, grid_for(L.n_frames, 256), 256, (const FrameRec*)L.frames.p, (const CandEnt*)L.cands.p, L.n_frames, W.first.p);
+	CL_TRY(dev_exclusive_scan_u32(ctx, W.first.p, L.n_frames, &W.ng));
+	const uint64_t ng = W.ng;
+	if (ng >= (1ull << 32)) return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_encode_reads: more than 2^32 gaps in one call");
+	L.n_gaps = (uint32_t)ng;
+	LAUNCH(ctx, k_frame_first_gaps, grid_for(L.n_frames, 256), 256, L.frames.p, (const uint32_t*)W.first.p, L.n_frames, L.n_gaps);
+	DEV_ALLOC(ctx, L.gaps, ng + 1);
+	DEV_ALLOC(ctx, W.capw, ng + 1); DEV_ALLOC(ctx, W.pflag, ng + 1); DEV_ALLOC(ctx, W.keys, ng + 1); DEV_ALLOC(ctx, W.ids, ng + 1);
+	LAUNCH(ctx, k_gap_geometry, grid_for(ng, 256), 256, L.view(), E.R, E.AV.data, E.cfg.min_part_alt, (const uint32_t*)W.first.p, W.capw.p, W.pflag.p, W.keys.p, W.ids.p, E.err);
+	DEV_ALLOC(ctx, W.es_off, ng + 1);
+	CL_TRY(dev_exclusive_scan_u64(ctx, W.capw.p, W.es_off.p, ng, &W.es_total));
+	CL_TRY(dev_exclusive_scan_u32(ctx, W.pflag.p, ng, &W.n_pend));
+	LAUNCH(ctx, k_gap_offsets, grid_for(ng, 256), 256, L.gaps.p, (const uint64_t*)W.es_off.p, L.n_gaps);
+	DEV_ALLOC(ctx, L.es, W.es_total + 16); DEV_ALLOC(ctx, L.pend, W.n_pend + 1); DEV_ALLOC(ctx, L.dec, W.n_pend + 1);
+	W.V = L.view();
+	return CL_OK;
+}
+
+// size classes: the gaps sorted by class and size; the class bounds hb (on a timing context each class's bytes and cells, h_cb, too) on the
+// host.  Host waits (main stream): the end of the sort (its temporaries go), then hb / h_cb: every aligner launch is sized by them
+cl_status level_size_classes(const EncCall& E, LevelBufs& L, LevelWork& W)
+{
+	cl_ctx* ctx = E.ctx; const uint64_t ng = W.ng;
+	CL_TRY(dev_sort_keys32_pairs(ctx, W.keys.p, W.ids.p, ng, 0, KEY_BITS));
+	DEV_ALLOC(ctx, W.bounds, N_CLASSES + 3);
+	HIP_TRY(ctx, hipMemsetAsync(W.bounds.p + N_CLASSES + 1, 0, 8, E.st));
+	LAUNCH(ctx, k_class_bounds, grid_for(ng + 1, 256), 256, (const uint32_t*)W.keys.p, (const uint32_t*)W.ids.p, (const uint32_t*)W.capw.p, L.n_gaps, W.bounds.p);
+	HIP_TRY(ctx, hipMemcpyAsync(W.hb, W.bounds.p, 4 * (N_CLASSES + 3), hipMemcpyDeviceToHost, E.st));
+	if (ctx->timing)
+	{
+		DevBuf<unsigned long long> cb; DEV_ALLOC(ctx, cb, 2 * N_CLASSES);
+		HIP_TRY(ctx, hipMemsetAsync(cb.p, 0, 16 * N_CLASSES, E.st));
+		LAUNCH(ctx, k_class_bytes, grid_for(ng, 256), 256, (const uint32_t*)W.keys.p, (const uint32_t*)W.ids.p, (const uint32_t*)W.capw.p, (const GapRec*)L.gaps.p, L.n_gaps, cb.p);
+		HIP_TRY(ctx, hipMemcpyAsync(W.h_cb, cb.p, 16 * N_CLASSES, hipMemcpyDeviceToHost, E.st));
+	}
+	HIP_TRY(ctx, hipStreamSynchronize(E.st));
+	return CL_OK;
+}
+
+// classes 1 - 4 (rows <= 64 NB, columns <= 256), one lane per gap with its state in LDS, on the stream `side`: next to the large ones on
+// the main stream (one wave per SIMD here, five waves per SIMD on a bump pool in HBM there: they share the machine well)
+struct SmallAligner {
+	DevBuf<uint64_t> hist;
+	StreamJoin join;
+	cl_status launch(const EncCall& E, LevelBufs& L, const LevelWork& W)
+	{
+		cl_ctx* ctx = E.ctx;
+		HIP_TRY(ctx, cl_side_stream(ctx, ctx->side));
+		join.s = ctx->side;
+		const uint32_t cap_blocks = E.n_cu * E.knobs.small_per_cu;
+		uint32_t max_blocks = 1;
+		for (int nb = 1; nb <= 4; ++nb) max_blocks = std::max(max_blocks, std::min<uint32_t>(grid_for(W.count(nb), 64), cap_blocks));
+		DEV_ALLOC(ctx, hist, (uint64_t)max_blocks * 256 * 4 * 2 * 64);
+		LaunchOn on(ctx, ctx->side);                                          // (launches + timing events on the side stream)
+		hipError_t le = hipSuccess;
+		for (int nb = 1; nb <= 4; ++nb)
+		{
+			const uint32_t n_list = W.count(nb);
+			if (!n_list) continue;
+			const uint32_t blocks = std::min<uint32_t>(grid_for(n_list, 64), cap_blocks);
+			const uint32_t lds = (12 * nb + 48) * 64 * 4;                       // LdsMem<nb>: QW + TW + EW words per lane
+			const double bytes = W.bytes(nb); const uint32_t* list = W.list(nb);
+			ctx->next_cells = W.cells(nb);
+			switch (nb)
+			{
+			case 1: LAUNCHB_SHM(ctx, bytes, (k_align_small<1>), blocks, 64, lds, list, n_list, L.gaps.p, L.es.p, E.A, E.R, hist.p); break;
+			case 2: LAUNCHB_SHM(ctx, bytes, (k_align_small<2>), blocks, 64, lds, list, n_list, L.gaps.p, L.es.p, E.A, E.R, hist.p); break;
+			case 3: LAUNCHB_SHM(ctx, bytes, (k_align_small<3>), blocks, 64, lds, list, n_list, L.gaps.p, L.es.p, E.A, E.R, hist.p); break;
+			default: LAUNCHB_SHM(ctx, bytes, (k_align_small<4>), blocks, 64, lds, list, n_list, L.gaps.p, L.es.p, E.A, E.R, hist.p); break;
+			}
+			if (le == hipSuccess) le = hipGetLastError();
+		}
+		HIP_TRY(ctx, le);
+		return CL_OK;
+	}
+	// Host wait (side).  (The guard stays armed: it joins the idle stream once more at the end of the level.)
+	cl_status wait(cl_ctx* ctx) { HIP_TRY(ctx, hipStreamSynchronize(ctx->side)); return CL_OK; }
+};
+
+// class 5 (up to 16 row blocks): four gaps per wave on the stream `side2` — a throughput kernel next to the wave-per-gap kernel, whose
+// launches last as long as their single slowest gap (measured: launch 61.5 ms, slowest gap 61.4 ms) and leave the machine idle
+// meanwhile.  The few gaps whose distance is beyond the band or whose buffers do not fit a wave's pool come back in `redo`.
+struct QuadAligner {
+	DevBuf<uint32_t> redo; DevBuf<uint8_t> scratch; DevBuf<unsigned int> cnt;
+	StreamJoin join;                                                         // armed from the first command on side2 to finish()
+	cl_status launch(const EncCall& E, uint32_t lv, LevelBufs& L, const LevelWork& W)
+	{
+		cl_ctx* ctx = E.ctx;
+		const uint32_t n_list = W.count(5);
+		if (!n_list) return CL_OK;
+		// 2.25 MB a wave: four banded histories of at most 512 KB; 2048 waves (4096 were no faster beside the other streams)
+		const uint64_t per_wave = 9ull << 18;
+		const uint32_t waves = std::min<uint32_t>((n_list + 3) / 4, E.knobs.quad_waves);
+		DEV_ALLOC(ctx, scratch, per_wave * waves);
+		DEV_ALLOC(ctx, cnt, 2);
+		DEV_ALLOC(ctx, redo, (uint64_t)n_list + 1);
+		HIP_TRY(ctx, cl_side_stream(ctx, ctx->side2));
+		join.s = ctx->side2;
+		HIP_TRY(ctx, hipMemsetAsync(cnt.p, 0, 8, ctx->side2));
+		LaunchOn on(ctx, ctx->side2);                                         // (launch + timing events on the third stream)
+		DevBuf<unsigned long long> qp;                                        // (COLORD_HIP_QUAD_PROFILE: the phases of the row kernel; waits for the launch)
+		if (E.knobs.quad_profile) { DEV_ALLOC(ctx, qp, 16); HIP_TRY(ctx, hipMemsetAsync(qp.p, 0, 128, ctx->side2)); }
+		ctx->next_cells = W.cells(5);
+		if (qp.p) LAUNCHB(ctx, W.bytes(5), k_align_quad_rows<true>, waves, 64, W.list(5), n_list, L.gaps.p, L.es.p, E.A, E.R, scratch.p, per_wave, cnt.p, redo.p, cnt.p + 1, qp.p);
+		else LAUNCHB(ctx, W.bytes(5), k_align_quad_rows<false>, waves, 64, W.list(5), n_list, L.gaps.p, L.es.p, E.A, E.R, scratch.p, per_wave, cnt.p, redo.p, cnt.p + 1, (unsigned long long*)nullptr);
+		if (qp.p) CL_TRY(diag::quad_profile(ctx, ctx->side2, qp.p, lv, n_list, waves));
+		HIP_TRY(ctx, hipGetLastError());
+		return CL_OK;
+	}
+	// Host wait (side2), if the level has class-5 gaps: how many of them the row kernel hands back
+	cl_status finish(cl_ctx* ctx, uint32_t& n_redo) { n_redo = 0; return join.s ? join.redo_count(ctx, cnt.p, n_redo) : CL_OK; }
+};
+
+// class 7, the giant gaps: many waves each (align_giant.hpp), on the stream `side3` from the start of the level, next to everything else
+struct GiantAligner {
+	DevBuf<uint32_t> redo; DevBuf<uint8_t> mem, heap, scratch; DevBuf<unsigned int> cnt;
+	StreamJoin join;                                                         // armed from the first command on side3 to finish()
+	bool running() const { return join.s != nullptr; }
+	cl_status launch(const EncCall& E, LevelBufs& L, const LevelWork& W)
+	{
+		cl_ctx* ctx = E.ctx;
+		const uint32_t n_list = W.count(7);
+		if (!n_list || E.knobs.no_team_align) return CL_OK;
+		const uint64_t sum_cap = (uint64_t)W.hb[N_CLASSES + 1] * 256, max_cap = W.hb[N_CLASSES + 2];
+		// sequences (4 copies), operations, sparse operations: 6 x (reference + read symbols) per gap; the last columns of a Hirschberg
+		// level: 8 bytes per row and level, the hand-over pairs 2 bits per column and tile
+		const uint64_t heap_bytes = std::min<uint64_t>(6ull << 30, (64ull << 20) + 100 * sum_cap + (uint64_t)n_list * 4096);
+		uint32_t phases = 2; for (uint64_t c = max_cap; c > 8 && phases < gt::MAX_PHASES; c >>= 1) ++phases;     // the columns halve per level; below ~16 everything is a leaf
+		auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
+		const uint64_t o_ctl = 0, o_flags = al(sizeof(gt::Ctl)), o_nodes = o_flags + al(4ull * gt::FLAG_CAP), o_sweeps = o_nodes + 2 * al(sizeof(gt::Node) * gt::NODE_CAP),
+			o_jobs = o_sweeps + 2 * al(sizeof(gt::Sweep) * 2 * gt::NODE_CAP), o_leaves = o_jobs + 2 * al(sizeof(gt::Job) * gt::JOB_CAP), o_giants = o_leaves + al(sizeof(gt::Leaf) * gt::LEAF_CAP),
+			o_end = o_giants + al(sizeof(gt::Giant) * n_list);
+		DEV_ALLOC(ctx, mem, o_end); DEV_ALLOC(ctx, heap, heap_bytes);
+		const uint32_t leaf_waves = 256; const uint64_t per_wave = 3ull << 20;     // a leaf's history is < 1 MiB twice over, + the reversed operations
+		const uint32_t fin_waves = std::min<uint32_t>(n_list, 64); const uint64_t fin_per_wave = (per_wave * leaf_waves) / 64;   // 12 MB: the canonicalisation's 9 bytes per script symbol
+		DEV_ALLOC(ctx, scratch, per_wave * leaf_waves);
+		DEV_ALLOC(ctx, cnt, 2);
+		DEV_ALLOC(ctx, redo, (uint64_t)n_list + 1);
+		HIP_TRY(ctx, cl_side_stream(ctx, ctx->side3));
+		join.s = ctx->side3;
+		HIP_TRY(ctx, hipMemsetAsync(cnt.p, 0, 8, ctx->side3));
+		HIP_TRY(ctx, hipMemsetAsync(mem.p, 0, o_nodes, ctx->side3));              // the control block and the progress words
+		gt::View V; V.ctl = (gt::Ctl*)(mem.p + o_ctl); V.heap = heap.p; V.heap_bytes = heap_bytes; V.flags = (uint32_t*)(mem.p + o_flags);
+		for (int i = 0; i < 2; ++i) { V.nodes[i] = (gt::Node*)(mem.p + o_nodes + i * al(sizeof(gt::Node) * gt::NODE_CAP)); V.sweeps[i] = (gt::Sweep*)(mem.p + o_sweeps + i * al(sizeof(gt::Sweep) * 2 * gt::NODE_CAP));
+			V.jobs[i] = (gt::Job*)(mem.p + o_jobs + i * al(sizeof(gt::Job) * gt::JOB_CAP)); }
+		V.leaves = (gt::Leaf*)(mem.p + o_leaves); V.giants = (gt::Giant*)(mem.p + o_giants); V.n_giants = n_list; V.n_phases = phases;
+		LaunchOn on(ctx, ctx->side3);
+		ctx->next_cells = W.cells(7);                                          // (booked on the staging launch: the class as a whole is what the report adds up)
+		LAUNCHB(ctx, W.bytes(7), k_giant_stage, n_list, 256, V, W.list(7), (const GapRec*)L.gaps.p, E.A, E.R);
+		for (uint32_t ph = 0; ph < phases; ++ph) LAUNCH(ctx, k_giant_level, 1024, 64, V, ph);
+		LAUNCH(ctx, k_giant_leaves, leaf_waves, 64, V, scratch.p, per_wave);
+		LAUNCH(ctx, k_giant_finish, fin_waves, 64, V, L.gaps.p, L.es.p, scratch.p, fin_per_wave, cnt.p, redo.p, cnt.p + 1);
+		HIP_TRY(ctx, hipGetLastError());
+		return CL_OK;
+	}
+	// Host wait (side3), if running(): how many giants the tile jobs hand back
+	cl_status finish(cl_ctx* ctx, uint32_t& n_redo) { return join.redo_count(ctx, cnt.p, n_redo); }
+};
+
+// class 6 and what the other aligners hand back: a wave per gap (k_align_wave) on the main stream, in rounds of growing pools.  3 MB a
+// wave: since the sweeps stop at the saturation row, sequences + operations + history of nearly every gap fit (a read flank of 200 kb:
+// 1.6 MB); the few others come back in the next round (x 8).  alg_bytes / cells are booked on round 0's launch.  level_class: the list
+// is the level's wave class, not a redo list.  Host waits (main stream), per round: its redo count; with gaps left, the copy of its redo list
+cl_status wave_rounds(const EncCall& E, uint32_t lv, LevelBufs& L, const LevelWork& W, const uint32_t* list, uint32_t n_list, double alg_bytes, double cells, bool level_class)
+{
+	cl_ctx* ctx = E.ctx; hipStream_t st = E.st;
+	if (n_list && E.knobs.gap_debug && level_class) CL_TRY(diag::wave_class_shapes(ctx, st, lv, L, W.hb, list, n_list));
+	DevBuf<uint32_t> todo, redo; DEV_ALLOC(ctx, todo, (uint64_t)n_list + 1); DEV_ALLOC(ctx, redo, (uint64_t)n_list + 1);
+	DevBuf<unsigned int> cnt; DEV_ALLOC(ctx, cnt, 2);
+	uint64_t per_wave = 3ull << 20; uint32_t max_waves = 2048;
+	DevBuf<unsigned long long> prof;
+	if (E.knobs.wave_profile) { DEV_ALLOC(ctx, prof, 16); HIP_TRY(ctx, hipMemsetAsync(prof.p, 0, 128, st)); }
+	uint32_t* hbt_dev = nullptr;
+	if (n_list && E.knobs.wave_heartbeat) CL_TRY(diag::wave_heartbeat(ctx, &hbt_dev));
+	for (int round = 0; n_list; ++round)
+	{
+		if (round == 5) return cl_fail(ctx, CL_E_NOMEM, "cl_encode_reads: lane pool exhausted (" + std::to_string(n_list) + " gaps left)");
+		const uint32_t waves = std::min<uint32_t>(n_list, max_waves);
+		DevBuf<uint8_t> scratch; DEV_ALLOC(ctx, scratch, per_wave * waves);
+		HIP_TRY(ctx, hipMemsetAsync(cnt.p, 0, 8, st));
+		const auto t_launch = std::chrono::steady_clock::now();               // (for the profile's line)
+		if (round == 0) ctx->next_cells = cells;
+		LAUNCHB(ctx, round == 0 ? alg_bytes : 0.0, k_align_wave, waves, 64, list, n_list, L.gaps.p, L.es.p, E.A, E.R, scratch.p, per_wave, cnt.p, redo.p, cnt.p + 1,
+			E.knobs.wave_debug_stage, hbt_dev, prof.p);
+		if (prof.p) CL_TRY(diag::wave_profile(ctx, st, prof.p, lv, n_list, waves, t_launch));
+		HIP_TRY(ctx, hipGetLastError());
+		unsigned int hc[2];
+		HIP_TRY(ctx, hipMemcpyAsync(hc, cnt.p, 8, hipMemcpyDeviceToHost, st));
+		HIP_TRY(ctx, hipStreamSynchronize(st));
+		n_list = hc[1];
+		if (n_list)
+		{
+			HIP_TRY(ctx, hipMemcpyAsync(todo.p, redo.p, (uint64_t)n_list * 4, hipMemcpyDeviceToDevice, st));
+			HIP_TRY(ctx, hipStreamSynchronize(st));
+			list = todo.p;
+			++ctx->gap_paths[10];                                               // a further round with larger pools
+		}
+		per_wave *= 8; max_waves = std::max<uint32_t>(max_waves / 8, 64);
+	}
+	return CL_OK;
+}
+
+// statistics / decisions of the level's gaps, and which of them get a child frame (k_spawn_mark refuses beyond max_rec: those gaps
+// become literals).  No host wait
+cl_status level_decisions(const EncCall& E, LevelBufs& L, const LevelWork& W, SpawnWork& S)
+{
+	cl_ctx* ctx = E.ctx; const uint64_t ng = W.ng;
+	DEV_ALLOC(ctx, S.sflag, ng + 1); DEV_ALLOC(ctx, S.sncand, ng + 1);
+	const uint32_t n_long = (uint32_t)(ng - W.n_pend);
+	DEV_ALLOC(ctx, S.long_list, (uint64_t)n_long + 1);
+	LAUNCH(ctx, k_gap_stats, grid_for(ng, 64), 64, W.V, E.A, E.cfg, (const uint32_t*)W.pflag.p, S.sflag.p, S.long_list.p);
+	if (n_long) LAUNCH(ctx, k_gap_stats_long, grid_for((uint64_t)n_long * 64, 256), 256, W.V, E.A, E.cfg, (const uint32_t*)S.long_list.p, n_long, S.sflag.p);
+	DEV_ALLOC(ctx, L.sums, ng + 1);
+	DEV_ALLOC(ctx, S.sum_long, ng + 2);                                        // ids of the gaps with long scripts, their number in the last word
+	HIP_TRY(ctx, hipMemsetAsync(S.sum_long.p + ng + 1, 0, 4, E.st));
+	LAUNCH(ctx, k_gap_sums, grid_for(ng, 64), 64, W.V, L.sums.p, S.sum_long.p, (unsigned int*)(S.sum_long.p + ng + 1));
+	LAUNCH(ctx, k_gap_sums_long, 1024, 256, W.V, L.sums.p, (const uint32_t*)S.sum_long.p, (const unsigned int*)(S.sum_long.p + ng + 1));
+	LAUNCH(ctx, k_spawn_mark, grid_for(ng, 64), 64, W.V, E.AV.data, E.cfg, S.sflag.p, S.sncand.p);
+	HIP_TRY(ctx, hipGetLastError());
+	return CL_OK;
+}
+
+// the next level's frames and candidates, added to `levels` — unless no gap spawned a frame: the level loop ends there.  Host waits (main
+// stream): two scan totals — candidates, frames — that size the child level, then the end of the level (its temporaries go)
+cl_status level_spawn(const EncCall& E, const LevelWork& W, SpawnWork& S, Levels& levels)
+{
+	cl_ctx* ctx = E.ctx; const uint64_t ng = W.ng;
+	auto N = std::make_unique<LevelBufs>();
+	DEV_ALLOC(ctx, S.cbase, ng + 1);
+	uint64_t nf = 0;
+	CL_TRY(dev_exclusive_scan_u64(ctx, S.sncand.p, S.cbase.p, ng, &N->n_cands));
+	CL_TRY(dev_exclusive_scan_u32(ctx, S.sflag.p, ng, &nf));
+	N->n_frames = (uint32_t)nf;
+	if (!nf) return CL_OK;
+	DEV_ALLOC(ctx, N->frames, nf + 1); DEV_ALLOC(ctx, N->cands, N->n_cands + 1);
+	LAUNCH(ctx, k_spawn_fill, grid_for(ng, 64), 64, W.V, E.AV.data, E.cfg, (const uint32_t*)S.sflag.p, (const uint64_t*)S.cbase.p, N->frames.p, N->cands.p);
+	HIP_TRY(ctx, hipGetLastError());
+	HIP_TRY(ctx, hipStreamSynchronize(E.st));
+	levels.push_back(std::move(N));
+	return CL_OK;
+}
+
+// estimator (per reader pack), then tuples: sizes, offsets, bytes.  Host waits (main stream): the scan totals of the estimator's events
+// and of the tuple bytes (checked against the caller's capacity), then the end of the call
+cl_status estimate_and_emit(const EncCall& E, const cl_reads* reads, const Levels& levels, const uint32_t* frame_of_read, const uint32_t* h_pack_bounds, uint32_t n_packs,
+                            uint8_t* d_es, uint64_t cap, uint64_t* d_es_off, uint32_t* d_es_ntuples, uint64_t* n_out)
+{
+	cl_ctx* ctx = E.ctx; const uint32_t nr = E.nr;
+	TreeV T; memset(&T, 0, sizeof(T));
+	for (size_t i = 0; i < levels.size() && i < 10; ++i) T.lv[i] = levels[i]->view();
+	T.frame_of_read = frame_of_read;
+	DevBuf<uint32_t> base_counts; DEV_ALLOC(ctx, base_counts, 4ull * nr);
+	LAUNCHB(ctx, reads->total_bases / 4.0, k_read_base_counts, grid_for((uint64_t)nr * 64, 256), 256, E.A, E.has_n, nr, base_counts.p);
+	DevBuf<uint32_t> d_pb; DEV_ALLOC(ctx, d_pb, (uint64_t)n_packs + 1);
+	HIP_TRY(ctx, hipMemcpyAsync(d_pb.p, h_pack_bounds, ((uint64_t)n_packs + 1) * 4, hipMemcpyHostToDevice, E.st));
+	DevBuf<uint32_t> ev_cnt; DEV_ALLOC(ctx, ev_cnt, (uint64_t)nr + 1);
+	DevBuf<uint64_t> ev_off; DEV_ALLOC(ctx, ev_off, (uint64_t)nr + 1);
+	LAUNCH(ctx, k_pend_count, grid_for(nr, 64), 64, T, nr, ev_cnt.p);
+	uint64_t n_events = 0;
+	CL_TRY(dev_exclusive_scan_u64(ctx, ev_cnt.p, ev_off.p, nr, &n_events));
+	DevBuf<uint32_t> events; DEV_ALLOC(ctx, events, n_events + 1);
+	LAUNCH(ctx, k_pend_list, grid_for(nr, 64), 64, T, nr, (const uint64_t*)ev_off.p, events.p);
+	if (n_packs) LAUNCH(ctx, k_estimator, n_packs, 64, T, (const uint32_t*)d_pb.p, n_packs, (const uint32_t*)reads->lens.p, E.has_n, (const uint32_t*)base_counts.p, (const uint64_t*)ev_off.p, (const uint32_t*)events.p);
+	DevBuf<uint32_t> sizes; DEV_ALLOC(ctx, sizes, nr);
+	uint64_t total = 0;
+	// one wave per read, the lanes over the fragments of a frame (emit_wave.hpp)
+	LAUNCHB(ctx, reads->total_bases * 1.25, k_emit_count_wave, grid_for(nr, 4), 256, E.A, T, nr, E.AV.data, sizes.p, d_es_ntuples);
+	HIP_TRY(ctx, hipGetLastError());
+	CL_TRY(dev_exclusive_scan_u64(ctx, sizes.p, d_es_off, nr, &total));
+	*n_out = total;
+	if (total > cap || (total && !d_es)) return cl_fail(ctx, CL_E_CAPACITY, "cl_encode_reads: need " + std::to_string(total) + " bytes");
+	LAUNCHB(ctx, reads->total_bases * 1.25 + (double)total, k_emit_write_wave, grid_for(nr, 4), 256, E.A, T, nr, E.AV.data, (const uint64_t*)d_es_off, d_es);
+	LAUNCH(ctx, k_emit_plain, grid_for(nr, 4), 256, E.A, (const uint32_t*)reads->inv.p, E.has_n, frame_of_read, nr, (const uint64_t*)d_es_off, d_es);
+	HIP_TRY(ctx, hipGetLastError());
+	HIP_TRY(ctx, hipStreamSynchronize(E.st));
+	return CL_OK;
+}
+} // namespace
 
 // CEncoder::Encode for all reads of the arena (encoder.cpp:1672-1691).  h_pack_bounds: the reader packs (the
 // estimator is reset at every pack).  Output: tuple streams (es_t bytes) back to back.
@@ -1088,387 +1440,52 @@ extern "C" cl_status cl_encode_reads(cl_ctx* ctx, const cl_reads* reads, const c
 	*n_out = 0;
 	for (uint64_t& x : ctx->gap_paths) x = 0;
 	if (!nr) return CL_OK;
-	ArenaV A{ reads->packed.p, reads->word_off.p, reads->lens.p }, R{ refs->packed.p, refs->word_off.p, refs->lens.p };
-	AnchorsV AV{ cl_anchors_n_cands(anchors), cl_anchors_cands(anchors), cl_anchors_cand_offsets(anchors), cl_anchors_data(anchors) };
-	const EncCfg cfg{ c, anchor_len, min_part_alt, max_rec, cost_mult };
-	const uint8_t* has_n = reads->has_n.p;
-	hipStream_t st = ctx->stream;
 
-	std::vector<std::unique_ptr<LevelBufs>> levels;
+	Levels levels;
 	DevBuf<uint32_t> frame_of_read; DEV_ALLOC(ctx, frame_of_read, nr);
 	DevBuf<uint32_t> err; DEV_ALLOC(ctx, err, 1);
-	HIP_TRY(ctx, hipMemsetAsync(err.p, 0, 4, st));
-	{	// level 0
-		auto L = std::make_unique<LevelBufs>();
-		DevBuf<uint32_t> flag, ncand; DEV_ALLOC(ctx, flag, (uint64_t)nr + 1); DEV_ALLOC(ctx, ncand, (uint64_t)nr + 1);
-		DevBuf<uint64_t> cbase; DEV_ALLOC(ctx, cbase, (uint64_t)nr + 1);
-		LAUNCH(ctx, k_read_flags, grid_for(nr, 256), 256, AV.n_cands, has_n, nr, flag.p, ncand.p);
-		uint64_t nf = 0;
-		CL_TRY(dev_exclusive_scan_u64(ctx, ncand.p, cbase.p, nr, &L->n_cands));
-		CL_TRY(dev_exclusive_scan_u32(ctx, flag.p, nr, &nf));
-		L->n_frames = (uint32_t)nf;
-		DEV_ALLOC(ctx, L->frames, nf + 1); DEV_ALLOC(ctx, L->cands, L->n_cands + 1);
-		LAUNCH(ctx, k_frames_level0, grid_for(nr, 256), 256, A, AV, c, has_n, nr, (const uint32_t*)flag.p, (const uint64_t*)cbase.p, L->frames.p, L->cands.p, frame_of_read.p);
-		HIP_TRY(ctx, hipGetLastError());
-		HIP_TRY(ctx, hipStreamSynchronize(st));
-		levels.push_back(std::move(L));
-	}
-	const uint32_t n_cu = (uint32_t)std::max(1, ctx->n_cu);                  // (cl_ctx_create: the device's multiProcessorCount)
+	HIP_TRY(ctx, hipMemsetAsync(err.p, 0, 4, ctx->stream));
+	const EncCall E{ ctx, ctx->stream, ArenaV{ reads->packed.p, reads->word_off.p, reads->lens.p }, ArenaV{ refs->packed.p, refs->word_off.p, refs->lens.p },
+		AnchorsV{ cl_anchors_n_cands(anchors), cl_anchors_cands(anchors), cl_anchors_cand_offsets(anchors), cl_anchors_data(anchors) },
+		EncCfg{ c, anchor_len, min_part_alt, max_rec, cost_mult }, reads->has_n.p, nr, (uint32_t)std::max(1, ctx->n_cu), err.p, EncKnobs::read() };
+	CL_TRY(level0_frames(E, frame_of_read.p, levels));                       // waits (main): 2 scan totals; the frames of level 0
 	for (uint32_t lv = 0; lv < levels.size(); ++lv)
 	{
 		LevelBufs& L = *levels[lv];
 		if (!L.n_frames) break;
-		// gaps of the level
-		DevBuf<uint32_t> first; DEV_ALLOC(ctx, first, (uint64_t)L.n_frames + 1);
-		LAUNCH(ctx, k_frame_gap_counts, grid_for(L.n_frames, 256), 256, (const FrameRec*)L.frames.p, (const CandEnt*)L.cands.p, L.n_frames, first.p);
-		uint64_t ng = 0;
-		CL_TRY(dev_exclusive_scan_u32(ctx, first.p, L.n_frames, &ng));
-		if (ng >= (1ull << 32)) return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_encode_reads: more than 2^32 gaps in one call");
-		L.n_gaps = (uint32_t)ng;
-		LAUNCH(ctx, k_frame_first_gaps, grid_for(L.n_frames, 256), 256, L.frames.p, (const uint32_t*)first.p, L.n_frames, L.n_gaps);
-		DEV_ALLOC(ctx, L.gaps, ng + 1);
-		DevBuf<uint32_t> capw, pflag, keys, ids; DEV_ALLOC(ctx, capw, ng + 1); DEV_ALLOC(ctx, pflag, ng + 1); DEV_ALLOC(ctx, keys, ng + 1); DEV_ALLOC(ctx, ids, ng + 1);
-		LevelV V = L.view();
-		LAUNCH(ctx, k_gap_geometry, grid_for(ng, 256), 256, V, R, AV.data, min_part_alt, (const uint32_t*)first.p, capw.p, pflag.p, keys.p, ids.p, err.p);
-		DevBuf<uint64_t> es_off; DEV_ALLOC(ctx, es_off, ng + 1);
-		uint64_t es_total = 0, n_pend = 0;
-		CL_TRY(dev_exclusive_scan_u64(ctx, capw.p, es_off.p, ng, &es_total));
-		CL_TRY(dev_exclusive_scan_u32(ctx, pflag.p, ng, &n_pend));
-		LAUNCH(ctx, k_gap_offsets, grid_for(ng, 256), 256, L.gaps.p, (const uint64_t*)es_off.p, L.n_gaps);
-		DEV_ALLOC(ctx, L.es, es_total + 16); DEV_ALLOC(ctx, L.pend, n_pend + 1); DEV_ALLOC(ctx, L.dec, n_pend + 1);
-		V = L.view();
-		// size classes
-		CL_TRY(dev_sort_keys32_pairs(ctx, keys.p, ids.p, ng, 0, KEY_BITS));
-		DevBuf<uint32_t> bounds; DEV_ALLOC(ctx, bounds, N_CLASSES + 3);
-		HIP_TRY(ctx, hipMemsetAsync(bounds.p + N_CLASSES + 1, 0, 8, st));
-		LAUNCH(ctx, k_class_bounds, grid_for(ng + 1, 256), 256, (const uint32_t*)keys.p, (const uint32_t*)ids.p, (const uint32_t*)capw.p, L.n_gaps, bounds.p);
-		uint32_t hb[N_CLASSES + 3];
-		unsigned long long h_cb[2 * N_CLASSES] = { 0 };                           // bytes, then DP cells, per class (timing runs only)
-		HIP_TRY(ctx, hipMemcpyAsync(hb, bounds.p, 4 * (N_CLASSES + 3), hipMemcpyDeviceToHost, st));
-		if (ctx->timing)
+		LevelWork W;
+		SmallAligner small; QuadAligner quad; GiantAligner giant;              // after W: their streams read W.ids, and they are joined before W goes
+		SpawnWork S;
+		uint32_t n_quad_redo = 0, n_giant_redo = 0;
+		CL_TRY(level_gaps(E, L, W));                                           // waits (main): 3 scan totals — gaps, script symbols, pending slots
+		CL_TRY(level_size_classes(E, L, W));                                   // waits (main): the sort's end; the class bounds that size every aligner launch
+		CL_TRY(small.launch(E, L, W));                                         // classes 1 - 4 on side
+		CL_TRY(quad.launch(E, lv, L, W));                                      // class 5 on side2
+		CL_TRY(giant.launch(E, L, W));                                         // class 7 on side3
+		CL_TRY(wave_rounds(E, lv, L, W, W.list(6), W.count(6), W.bytes(6), W.cells(6), true));   // class 6 on main; waits (main): each round's redo count
+		CL_TRY(quad.finish(ctx, n_quad_redo));                                 // waits (side2): class 5 is through; its redo count
+		if (n_quad_redo) CL_TRY(wave_rounds(E, lv, L, W, quad.redo.p, n_quad_redo, 0.0, 0.0, false));
+		if (giant.running())
 		{
-			DevBuf<unsigned long long> cb; DEV_ALLOC(ctx, cb, 2 * N_CLASSES);
-			HIP_TRY(ctx, hipMemsetAsync(cb.p, 0, 16 * N_CLASSES, st));
-			LAUNCH(ctx, k_class_bytes, grid_for(ng, 256), 256, (const uint32_t*)keys.p, (const uint32_t*)ids.p, (const uint32_t*)capw.p, (const GapRec*)L.gaps.p, L.n_gaps, cb.p);
-			HIP_TRY(ctx, hipMemcpyAsync(h_cb, cb.p, 16 * N_CLASSES, hipMemcpyDeviceToHost, st));
+			CL_TRY(giant.finish(ctx, n_giant_redo));                             // waits (side3): class 7 is through; its redo count
+			if (E.knobs.gap_debug) diag::giant_line(lv, W.hb, n_giant_redo);
 		}
-		HIP_TRY(ctx, hipStreamSynchronize(st));
-		// small gaps: on the side stream, next to the large ones on the main stream (one wave per SIMD with its state in
-		// LDS here, five waves per SIMD on a bump pool in HBM there: they share the machine well)
-		HIP_TRY(ctx, cl_side_stream(ctx, ctx->side));
-		struct SideJoin { hipStream_t s; ~SideJoin() { (void)hipStreamSynchronize(s); } };
-		DevBuf<uint64_t> hist;
-		SideJoin side_join{ ctx->side };                                         // (after hist in destruction order: joins first)
-		{
-			uint32_t max_blocks = 1;
-			static const uint32_t small_per_cu = getenv("COLORD_HIP_SMALL_PER_CU") ? (uint32_t)std::max(1, atoi(getenv("COLORD_HIP_SMALL_PER_CU"))) : 4u;   // (tuning knob: blocks of 15 - 25 KB of LDS each)
-			for (int nb = 1; nb <= 4; ++nb) max_blocks = std::max(max_blocks, std::min<uint32_t>(grid_for(hb[nb + 1] - hb[nb], 64), n_cu * small_per_cu));
-			DEV_ALLOC(ctx, hist, (uint64_t)max_blocks * 256 * 4 * 2 * 64);
-			LaunchOn on(ctx, ctx->side);                                          // (launches + timing events on the side stream)
-			hipError_t le = hipSuccess;
-			for (int nb = 1; nb <= 4; ++nb)
-			{
-				const uint32_t n_list = hb[nb + 1] - hb[nb];
-				if (!n_list) continue;
-				const uint32_t blocks = std::min<uint32_t>(grid_for(n_list, 64), n_cu * small_per_cu);
-				const uint32_t lds = (12 * nb + 48) * 64 * 4;                       // LdsMem<nb>: QW + TW + EW words per lane
-				const double bytes = 1.25 * (double)h_cb[nb];
-				ctx->next_cells = (double)h_cb[N_CLASSES + nb];
-				const uint32_t* list = ids.p + hb[nb];
-				switch (nb)
-				{
-				case 1: LAUNCHB_SHM(ctx, bytes, (k_align_small<1>), blocks, 64, lds, list, n_list, L.gaps.p, L.es.p, A, R, hist.p); break;
-				case 2: LAUNCHB_SHM(ctx, bytes, (k_align_small<2>), blocks, 64, lds, list, n_list, L.gaps.p, L.es.p, A, R, hist.p); break;
-				case 3: LAUNCHB_SHM(ctx, bytes, (k_align_small<3>), blocks, 64, lds, list, n_list, L.gaps.p, L.es.p, A, R, hist.p); break;
-				default: LAUNCHB_SHM(ctx, bytes, (k_align_small<4>), blocks, 64, lds, list, n_list, L.gaps.p, L.es.p, A, R, hist.p); break;
-				}
-				if (le == hipSuccess) le = hipGetLastError();
-			}
-			HIP_TRY(ctx, le);
-		}
-		// gaps of up to 16 row blocks: four per wave, on a third stream — a throughput kernel next to the wave-per-gap kernel
-		// below, whose launches last as long as their single slowest gap (measured: launch 61.5 ms, slowest gap 61.4 ms) and
-		// leave the machine idle meanwhile.  The few gaps whose buffers do not fit a wave's pool come back in quad_redo.
-		DevBuf<uint32_t> quad_redo; uint32_t n_quad_redo = 0;
-		DevBuf<uint8_t> quad_scratch; DevBuf<unsigned int> qc;
-		struct Side2Join { hipStream_t s = nullptr; ~Side2Join() { if (s) (void)hipStreamSynchronize(s); } } quad_join;   // (after the buffers in destruction order)
-		if (hb[6] > hb[5])
-		{
-			const uint32_t n_list = hb[6] - hb[5];
-			// 2.25 MB a wave: four banded histories of at most 512 KB; 2048 waves (4096 were no faster beside the other streams)
-			const uint64_t per_wave = 9ull << 18;
-			static const uint32_t quad_waves = getenv("COLORD_HIP_QUAD_WAVES") ? (uint32_t)std::max(64, atoi(getenv("COLORD_HIP_QUAD_WAVES"))) : 2048u;   // (tuning knob: waves of 18.5 KB of LDS each)
-			const uint32_t waves = std::min<uint32_t>((n_list + 3) / 4, quad_waves);
-			DEV_ALLOC(ctx, quad_scratch, per_wave * waves);
-			DEV_ALLOC(ctx, qc, 2);
-			DEV_ALLOC(ctx, quad_redo, (uint64_t)n_list + 1);
-			HIP_TRY(ctx, cl_side_stream(ctx, ctx->side2));
-			quad_join.s = ctx->side2;
-			HIP_TRY(ctx, hipMemsetAsync(qc.p, 0, 8, ctx->side2));
-			LaunchOn on(ctx, ctx->side2);                                         // (launch + timing events on the third stream)
-			ctx->next_cells = (double)h_cb[N_CLASSES + 5];
-			static const bool quad_prof = getenv("COLORD_HIP_QUAD_PROFILE") != nullptr;
-			if (quad_prof)
-			{	// diagnostic: the phases of the row kernel (waits for the launch)
-				DevBuf<unsigned long long> qp; DEV_ALLOC(ctx, qp, 16);
-				HIP_TRY(ctx, hipMemsetAsync(qp.p, 0, 128, ctx->side2));
-				LAUNCHB(ctx, 1.25 * (double)h_cb[5], k_align_quad_rows<true>, waves, 64, (const uint32_t*)ids.p + hb[5], n_list, L.gaps.p, L.es.p, A, R, quad_scratch.p, per_wave, qc.p, quad_redo.p, qc.p + 1, qp.p);
-				unsigned long long hp[16];
-				HIP_TRY(ctx, hipStreamSynchronize(ctx->side2));
-				HIP_TRY(ctx, hipMemcpy(hp, qp.p, 128, hipMemcpyDeviceToHost));
-				const double q = (double)std::max<unsigned long long>(hp[9], 1);
-				fprintf(stderr, "[quad rows, level %u] %u gaps in %llu quads on %u waves; us per quad: stage %.1f sweep %.1f walk %.1f convert %.1f refactor %.1f fetch+write %.1f; sweep steps per quad %.0f; walk iterations per quad %.0f, of which waited for new windows %.1f\n",
-					lv, n_list, hp[9], waves, hp[0] / q / 100.0, hp[1] / q / 100.0, hp[2] / q / 100.0, hp[3] / q / 100.0, hp[4] / q / 100.0, hp[5] / q / 100.0, hp[10] / q, hp[6] / q, hp[7] / q);
-			}
-			else LAUNCHB(ctx, 1.25 * (double)h_cb[5], k_align_quad_rows<false>, waves, 64, (const uint32_t*)ids.p + hb[5], n_list, L.gaps.p, L.es.p, A, R, quad_scratch.p, per_wave, qc.p, quad_redo.p, qc.p + 1, (unsigned long long*)nullptr);
-			HIP_TRY(ctx, hipGetLastError());
-		}
-		// giant gaps: many waves each (align_giant.hpp), on a stream of their own from the start of the level, next to everything else
-		DevBuf<uint32_t> team_redo; uint32_t n_team_redo = 0;
-		DevBuf<uint8_t> giant_mem, giant_heap, giant_scratch; DevBuf<unsigned int> tc;
-		Side2Join team_join;
-		if (hb[8] > hb[7] && !getenv("COLORD_HIP_NO_TEAM_ALIGN"))
-		{
-			const uint32_t n_list = hb[8] - hb[7];
-			const uint64_t sum_cap = (uint64_t)hb[N_CLASSES + 1] * 256, max_cap = hb[N_CLASSES + 2];
-			// sequences (4 copies), operations, sparse operations: 6 x (reference + read symbols) per gap; the last columns of a Hirschberg
-			// level: 8 bytes per row and level, the hand-over pairs 2 bits per column and tile
-			const uint64_t heap_bytes = std::min<uint64_t>(6ull << 30, (64ull << 20) + 100 * sum_cap + (uint64_t)n_list * 4096);
-			uint32_t phases = 2; for (uint64_t c = max_cap; c > 8 && phases < gt::MAX_PHASES; c >>= 1) ++phases;     // the columns halve per level; below ~16 everything is a leaf
-			auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
-			const uint64_t o_ctl = 0, o_flags = al(sizeof(gt::Ctl)), o_nodes = o_flags + al(4ull * gt::FLAG_CAP), o_sweeps = o_nodes + 2 * al(sizeof(gt::Node) * gt::NODE_CAP),
-				o_jobs = o_sweeps + 2 * al(sizeof(gt::Sweep) * 2 * gt::NODE_CAP), o_leaves = o_jobs + 2 * al(sizeof(gt::Job) * gt::JOB_CAP), o_giants = o_leaves + al(sizeof(gt::Leaf) * gt::LEAF_CAP),
-				o_end = o_giants + al(sizeof(gt::Giant) * n_list);
-			DEV_ALLOC(ctx, giant_mem, o_end); DEV_ALLOC(ctx, giant_heap, heap_bytes);
-			const uint32_t leaf_waves = 256; const uint64_t per_wave = 3ull << 20;     // a leaf's history is < 1 MiB twice over, + the reversed operations
-			const uint32_t fin_waves = std::min<uint32_t>(n_list, 64); const uint64_t fin_per_wave = (per_wave * leaf_waves) / 64;   // 12 MB: the canonicalisation's 9 bytes per script symbol
-			DEV_ALLOC(ctx, giant_scratch, per_wave * leaf_waves);
-			DEV_ALLOC(ctx, tc, 2);
-			DEV_ALLOC(ctx, team_redo, (uint64_t)n_list + 1);
-			HIP_TRY(ctx, cl_side_stream(ctx, ctx->side3));
-			team_join.s = ctx->side3;
-			HIP_TRY(ctx, hipMemsetAsync(tc.p, 0, 8, ctx->side3));
-			HIP_TRY(ctx, hipMemsetAsync(giant_mem.p, 0, o_nodes, ctx->side3));       // the control block and the progress words
-			gt::View V; V.ctl = (gt::Ctl*)(giant_mem.p + o_ctl); V.heap = giant_heap.p; V.heap_bytes = heap_bytes; V.flags = (uint32_t*)(giant_mem.p + o_flags);
-			for (int i = 0; i < 2; ++i) { V.nodes[i] = (gt::Node*)(giant_mem.p + o_nodes + i * al(sizeof(gt::Node) * gt::NODE_CAP)); V.sweeps[i] = (gt::Sweep*)(giant_mem.p + o_sweeps + i * al(sizeof(gt::Sweep) * 2 * gt::NODE_CAP));
-				V.jobs[i] = (gt::Job*)(giant_mem.p + o_jobs + i * al(sizeof(gt::Job) * gt::JOB_CAP)); }
-			V.leaves = (gt::Leaf*)(giant_mem.p + o_leaves); V.giants = (gt::Giant*)(giant_mem.p + o_giants); V.n_giants = n_list; V.n_phases = phases;
-			LaunchOn on(ctx, ctx->side3);
-			ctx->next_cells = (double)h_cb[N_CLASSES + 7];                         // (booked on the staging launch: the class as a whole is what the report adds up)
-			LAUNCHB(ctx, 1.25 * (double)h_cb[7], k_giant_stage, n_list, 256, V, (const uint32_t*)ids.p + hb[7], (const GapRec*)L.gaps.p, A, R);
-			for (uint32_t ph = 0; ph < phases; ++ph) LAUNCH(ctx, k_giant_level, 1024, 64, V, ph);
-			LAUNCH(ctx, k_giant_leaves, leaf_waves, 64, V, giant_scratch.p, per_wave);
-			LAUNCH(ctx, k_giant_finish, fin_waves, 64, V, L.gaps.p, L.es.p, giant_scratch.p, fin_per_wave, tc.p, team_redo.p, tc.p + 1);
-			HIP_TRY(ctx, hipGetLastError());
-		}
-		// large gaps, in rounds of growing lane pools
-		auto run_large = [&](const uint32_t* list, uint32_t n_list, double alg_bytes) -> cl_status
-		{
-			if (n_list && getenv("COLORD_HIP_GAP_DEBUG") && list == ids.p + hb[6])
-			{	// diagnostic: shapes of the wave-class gaps of the level (the list is ascending in log2 of the work)
-				HIP_TRY(ctx, hipStreamSynchronize(st));
-				std::vector<uint32_t> h_ids(n_list);
-				HIP_TRY(ctx, hipMemcpy(h_ids.data(), list, (uint64_t)n_list * 4, hipMemcpyDeviceToHost));
-				std::vector<GapRec> all(L.n_gaps);
-				HIP_TRY(ctx, hipMemcpy(all.data(), L.gaps.p, (uint64_t)L.n_gaps * sizeof(GapRec), hipMemcpyDeviceToHost));
-				double work = 0, steps = 0; std::string txt; uint64_t hist[8] = { 0 }; double hwork[8] = { 0 };
-				for (uint32_t i = 0; i < n_list; ++i)
-				{
-					const GapRec& t = all[h_ids[n_list - 1 - i]];
-					const uint32_t rows = t.kind == GK_FLANK ? t.ne : t.use, cols = t.kind == GK_FLANK ? t.use : t.ne;
-					const double w = (double)((rows + 63) / 64) * cols, st_ = (double)((rows + 4095) / 4096) * (cols + 63);
-					work += w; steps += st_;
-					const int b = rows <= 256 ? 0 : rows <= 1024 ? 1 : rows <= 4096 ? 2 : rows <= 16384 ? 3 : 4;
-					hist[b]++; hwork[b] += st_;
-					if (i < 8) txt += " " + std::string(t.kind == GK_FLANK ? "F" : "I") + std::to_string(rows) + "x" + std::to_string(cols);
-				}
-				fprintf(stderr, "[gaps] level %u: classes 1-4 %u, quad %u, wave %u; wave class: block-columns %.3g, sweep steps %.3g; by rows <=256 %llu (%.3g steps) <=1024 %llu (%.3g) <=4096 %llu (%.3g) <=16384 %llu (%.3g) more %llu (%.3g); largest:%s\n",
-					lv, hb[5] - hb[1], hb[6] - hb[5], n_list, work, steps, (unsigned long long)hist[0], hwork[0], (unsigned long long)hist[1], hwork[1], (unsigned long long)hist[2], hwork[2],
-					(unsigned long long)hist[3], hwork[3], (unsigned long long)hist[4], hwork[4], txt.c_str());
-			}
-			DevBuf<uint32_t> todo, redo; DEV_ALLOC(ctx, todo, (uint64_t)n_list + 1); DEV_ALLOC(ctx, redo, (uint64_t)n_list + 1);
-			DevBuf<unsigned int> cnt; DEV_ALLOC(ctx, cnt, 2);
-			// waves (k_align_wave) / lanes (k_align_large).  3 MB a wave: since the sweeps stop at the saturation row, sequences + operations
-			// + history of nearly every gap fit (a read flank of 200 kb: 1.6 MB); the few others come back in the next round (x 8)
-			uint64_t per_lane = 3ull << 20; uint32_t max_lanes = 2048;
-			const bool use_wave = getenv("COLORD_HIP_NO_WAVE_ALIGN") == nullptr;
-			DevBuf<unsigned long long> prof;
-			if (getenv("COLORD_HIP_WAVE_PROFILE")) { DEV_ALLOC(ctx, prof, 16); HIP_TRY(ctx, hipMemsetAsync(prof.p, 0, 128, st)); }
-			uint32_t* hbt_host = nullptr; uint32_t* hbt_dev = nullptr;
-			if (use_wave && n_list && getenv("COLORD_HIP_WAVE_HEARTBEAT"))
-			{	// debugging: host-visible progress words, dumped by a watchdog thread if the kernel is still running after a while
-				HIP_TRY(ctx, hipHostMalloc((void**)&hbt_host, 4096 * 4, hipHostMallocMapped));
-				memset(hbt_host, 0, 4096 * 4);
-				HIP_TRY(ctx, hipHostGetDevicePointer((void**)&hbt_dev, hbt_host, 0));
-				std::thread([hbt_host]() { for (int t = 0; t < 3; ++t) { std::this_thread::sleep_for(std::chrono::seconds(8)); fprintf(stderr, "[heartbeat]");
-					for (int i = 0; i < 24; ++i) fprintf(stderr, " %u", hbt_host[i]); fprintf(stderr, "\n"); fflush(stderr); } }).detach();
-			}
-			for (int round = 0; n_list; ++round)
-			{
-				if (round == 5) return cl_fail(ctx, CL_E_NOMEM, "cl_encode_reads: lane pool exhausted (" + std::to_string(n_list) + " gaps left)");
-				const uint32_t lanes = use_wave ? std::min<uint32_t>(n_list, max_lanes) : (uint32_t)std::min<uint64_t>(((uint64_t)n_list + 63) / 64 * 64, max_lanes);
-				DevBuf<uint8_t> scratch; DEV_ALLOC(ctx, scratch, per_lane * lanes);
-				HIP_TRY(ctx, hipMemsetAsync(cnt.p, 0, 8, st));
-				if (use_wave)
-				{
-				const auto t_launch = std::chrono::steady_clock::now();
-				LAUNCHB(ctx, round == 0 ? alg_bytes : 0.0, k_align_wave, lanes, 64, list, n_list, L.gaps.p, L.es.p, A, R, scratch.p, per_lane, cnt.p, redo.p, cnt.p + 1,
-					(uint32_t)(getenv("COLORD_HIP_WAVE_DEBUG_STAGE") ? atoi(getenv("COLORD_HIP_WAVE_DEBUG_STAGE")) : 0), hbt_dev, prof.p);
-				if (prof.p)
-				{
-					unsigned long long hp[16];
-					HIP_TRY(ctx, hipStreamSynchronize(st));
-					HIP_TRY(ctx, hipMemcpy(hp, prof.p, 128, hipMemcpyDeviceToHost));
-					fprintf(stderr, "[slowest gap, level %u] kind %llu read symbols %llu reference symbols %llu: stage %.2f sweep %.2f path %.2f convert %.2f refactor %.2f ms\n", lv, hp[15], hp[14] >> 32, hp[14] & 0xffffffffull,
-						hp[9] / 1e5, hp[10] / 1e5, hp[11] / 1e5, hp[12] / 1e5, hp[13] / 1e5);
-					fprintf(stderr, "[wave phases, level %u, %u gaps, Mcycles of 100 MHz] alloc %llu stage %llu sweep %llu path %llu convert %llu refactor %llu fetch %llu; slowest gap %.2f ms (rank %llu from the largest); launch of %u waves %.1f ms\n", lv, n_list,
-						hp[0] / 1000000, hp[1] / 1000000, hp[2] / 1000000, hp[3] / 1000000, hp[4] / 1000000, hp[5] / 1000000, hp[7] / 1000000, (double)(hp[6] >> 24) / 1e5, hp[6] & 0xffffffull, lanes, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_launch).count());
-				}
-				}
-				else LAUNCH(ctx, k_align_large, lanes / 64, 64, list, n_list, L.gaps.p, L.es.p, A, R, scratch.p, per_lane, cnt.p, redo.p, cnt.p + 1);
-				HIP_TRY(ctx, hipGetLastError());
-				unsigned int hc[2];
-				HIP_TRY(ctx, hipMemcpyAsync(hc, cnt.p, 8, hipMemcpyDeviceToHost, st));
-				HIP_TRY(ctx, hipStreamSynchronize(st));
-				n_list = hc[1];
-				if (n_list)
-				{
-					HIP_TRY(ctx, hipMemcpyAsync(todo.p, redo.p, (uint64_t)n_list * 4, hipMemcpyDeviceToDevice, st));
-					HIP_TRY(ctx, hipStreamSynchronize(st));
-					list = todo.p;
-				}
-				if (n_list) ++ctx->gap_paths[10];                                     // a further round with larger pools
-				per_lane *= 8; max_lanes = std::max<uint32_t>(max_lanes / 8, 64);
-			}
-			return CL_OK;
-		};
-		ctx->next_cells = (double)h_cb[N_CLASSES + 6];
-		CL_TRY(run_large(ids.p + hb[6], hb[7] - hb[6], 1.25 * (double)h_cb[6]));
-		if (quad_join.s)
-		{
-			unsigned int hc[2];
-			HIP_TRY(ctx, hipMemcpyAsync(hc, qc.p, 8, hipMemcpyDeviceToHost, ctx->side2));
-			HIP_TRY(ctx, hipStreamSynchronize(ctx->side2));
-			quad_join.s = nullptr;
-			n_quad_redo = hc[1];
-		}
-		if (n_quad_redo) CL_TRY(run_large(quad_redo.p, n_quad_redo, 0.0));
-		if (team_join.s)
-		{
-			unsigned int hc[2];
-			HIP_TRY(ctx, hipMemcpyAsync(hc, tc.p, 8, hipMemcpyDeviceToHost, ctx->side3));
-			HIP_TRY(ctx, hipStreamSynchronize(ctx->side3));
-			team_join.s = nullptr;
-			n_team_redo = hc[1];
-			if (getenv("COLORD_HIP_GAP_DEBUG")) fprintf(stderr, "[gaps] level %u: %u giant gaps by tile jobs (largest script %u symbols), %u back to the wave kernel\n", lv, hb[8] - hb[7], hb[N_CLASSES + 2], n_team_redo);
-		}
-		else if (hb[8] > hb[7]) CL_TRY(run_large(ids.p + hb[7], hb[8] - hb[7], 1.25 * (double)h_cb[7]));   // (COLORD_HIP_NO_TEAM_ALIGN)
-		if (n_team_redo) CL_TRY(run_large(team_redo.p, n_team_redo, 0.0));
-		for (uint32_t cls = 0; cls < N_CLASSES; ++cls) ctx->gap_paths[cls] += hb[cls + 1] - hb[cls];
-		ctx->gap_paths[8] += n_quad_redo; ctx->gap_paths[9] += n_team_redo;
-		if (getenv("COLORD_HIP_GAP_DEBUG"))
-			fprintf(stderr, "[gaps] level %u: per class %u %u %u %u %u %u %u %u; quad -> wave %u, giant -> wave %u; wave-pool redo rounds of the call so far %llu\n", lv, hb[1] - hb[0], hb[2] - hb[1],
-				hb[3] - hb[2], hb[4] - hb[3], hb[5] - hb[4], hb[6] - hb[5], hb[7] - hb[6], hb[8] - hb[7], n_quad_redo, n_team_redo, (unsigned long long)ctx->gap_paths[10]);
-		HIP_TRY(ctx, hipStreamSynchronize(ctx->side));                           // the small gaps are through
-		if (getenv("COLORD_HIP_GAP_SHAPES"))
-		{	// diagnostic: shapes and edit distances of the aligned gaps by class — what a band (edlib.cpp:192-212) would save, what fits LDS
-			HIP_TRY(ctx, hipDeviceSynchronize());
-			std::vector<GapRec> all(L.n_gaps); std::vector<char> hes(es_total + 16);
-			HIP_TRY(ctx, hipMemcpy(all.data(), L.gaps.p, (uint64_t)L.n_gaps * sizeof(GapRec), hipMemcpyDeviceToHost));
-			HIP_TRY(ctx, hipMemcpy(hes.data(), L.es.p, es_total, hipMemcpyDeviceToHost));
-			struct Acc { uint64_t n = 0; double cells = 0, band = 0, band_ideal = 0; std::vector<uint32_t> nm, dpm; uint64_t ratio[11] = { 0 }; } acc[N_CLASSES + 1];
-			for (const GapRec& g : all)
-			{
-				if (g.kind == GK_TRIVIAL) continue;
-				const uint32_t rows = g.kind == GK_FLANK ? g.ne : g.use, cols = g.kind == GK_FLANK ? g.use : g.ne;      // (gap_class, restated for the host)
-				const uint32_t cls = (rows <= 256 && cols <= 256) ? (rows + 63) / 64 : (rows <= QUAD_ROWS && rows + cols <= QUAD_SEQ && (uint64_t)((rows + 63) / 64) * (cols + 16) <= QUAD_CELLS) ? 5u
-					: (rows > GIANT_ROWS && rows <= GIANT_MAX_ROWS && (uint64_t)((rows + 63) / 64) * cols >= GIANT_WORK && rows / 8 < cols) ? 7u : 6u;
-				if (!cls || !rows || !cols) continue;
-				uint32_t d = 0; for (uint32_t x = 0; x < g.es_len; ++x) d += hes[g.es_off + x] != 'M';
-				Acc& a = acc[cls]; ++a.n;
-				const double nb = (rows + 63) / 64; a.cells += nb * cols;
-				// edlib's k-doubling (edlib.cpp:192-212: k = 64, 128, ... until the score fits) with Ukkonen's band of 2 k + |rows - cols| + 1 rows
-				const double diff = rows > cols ? rows - cols : cols - rows;
-				auto bandw = [&](double k) { return std::min(nb, std::ceil((2 * k + diff + 1) / 64.0) + 1); };
-				double k = 64, cost = 0; while (k < d) { cost += bandw(k) * cols * 0.5; k *= 2; }   // (a failed round stops about half way)
-				a.band += cost + bandw(k) * cols; a.band_ideal += bandw(d) * cols;
-				a.nm.push_back(rows + cols); a.dpm.push_back((uint32_t)(1000.0 * d / std::max(rows, cols)));
-				a.ratio[std::min<uint32_t>(10, (uint32_t)(20.0 * d / std::max(rows, cols)))]++;
-			}
-			for (uint32_t cls = 1; cls <= N_CLASSES; ++cls)
-			{
-				Acc& a = acc[cls]; if (!a.n) continue;
-				std::sort(a.nm.begin(), a.nm.end()); std::sort(a.dpm.begin(), a.dpm.end());
-				auto pc = [&](std::vector<uint32_t>& v, double p) { return v[std::min<size_t>(v.size() - 1, (size_t)(p * v.size()))]; };
-				auto le = [&](uint32_t x) { return (double)(std::upper_bound(a.nm.begin(), a.nm.end(), x) - a.nm.begin()) / a.n; };
-				fprintf(stderr, "[shapes] level %u class %u: %llu gaps, block-columns %.4g, k-doubling band %.4g (%.2f), band of the true distance %.4g (%.2f); rows+cols p50 %u p90 %u p99 %u p99.9 %u max %u; <=1536 %.4f <=2048 %.4f <=2730 %.4f <=4096 %.4f; d/len permille p10 %u p50 %u p90 %u p99 %u; by d/len in steps of 5%%:",
-					lv, cls, (unsigned long long)a.n, a.cells, a.band, a.band / a.cells, a.band_ideal, a.band_ideal / a.cells, pc(a.nm, 0.5), pc(a.nm, 0.9), pc(a.nm, 0.99), pc(a.nm, 0.999), a.nm.back(),
-					le(1536), le(2048), le(2730), le(4096), pc(a.dpm, 0.1), pc(a.dpm, 0.5), pc(a.dpm, 0.9), pc(a.dpm, 0.99));
-				for (int i = 0; i < 11; ++i) fprintf(stderr, " %llu", (unsigned long long)a.ratio[i]);
-				fprintf(stderr, "\n");
-			}
-		}
-		// statistics / decisions, children
-		DevBuf<uint32_t> sflag, sncand; DEV_ALLOC(ctx, sflag, ng + 1); DEV_ALLOC(ctx, sncand, ng + 1);
-		const uint32_t n_long = (uint32_t)(ng - n_pend);
-		DevBuf<uint32_t> long_list; DEV_ALLOC(ctx, long_list, (uint64_t)n_long + 1);
-		LAUNCH(ctx, k_gap_stats, grid_for(ng, 64), 64, V, A, cfg, (const uint32_t*)pflag.p, sflag.p, long_list.p);
-		if (n_long) LAUNCH(ctx, k_gap_stats_long, grid_for((uint64_t)n_long * 64, 256), 256, V, A, cfg, (const uint32_t*)long_list.p, n_long, sflag.p);
-		DEV_ALLOC(ctx, L.sums, ng + 1);
-		DevBuf<uint32_t> sum_long; DEV_ALLOC(ctx, sum_long, ng + 2);                // ids of the gaps with long scripts, their number in the last word
-		HIP_TRY(ctx, hipMemsetAsync(sum_long.p + ng + 1, 0, 4, st));
-		LAUNCH(ctx, k_gap_sums, grid_for(ng, 64), 64, V, L.sums.p, sum_long.p, (unsigned int*)(sum_long.p + ng + 1));
-		LAUNCH(ctx, k_gap_sums_long, 1024, 256, V, L.sums.p, (const uint32_t*)sum_long.p, (const unsigned int*)(sum_long.p + ng + 1));
-		LAUNCH(ctx, k_spawn_mark, grid_for(ng, 64), 64, V, AV.data, cfg, sflag.p, sncand.p);      // refuses beyond max_rec: those gaps become literals
-		HIP_TRY(ctx, hipGetLastError());
-		if (lv >= max_rec || lv + 1 >= 10) { HIP_TRY(ctx, hipStreamSynchronize(st)); break; }
-		auto N = std::make_unique<LevelBufs>();
-		DevBuf<uint64_t> cbase; DEV_ALLOC(ctx, cbase, ng + 1);
-		uint64_t nf = 0;
-		CL_TRY(dev_exclusive_scan_u64(ctx, sncand.p, cbase.p, ng, &N->n_cands));
-		CL_TRY(dev_exclusive_scan_u32(ctx, sflag.p, ng, &nf));
-		N->n_frames = (uint32_t)nf;
-		if (!nf) break;
-		DEV_ALLOC(ctx, N->frames, nf + 1); DEV_ALLOC(ctx, N->cands, N->n_cands + 1);
-		LAUNCH(ctx, k_spawn_fill, grid_for(ng, 64), 64, V, AV.data, cfg, (const uint32_t*)sflag.p, (const uint64_t*)cbase.p, N->frames.p, N->cands.p);
-		HIP_TRY(ctx, hipGetLastError());
-		HIP_TRY(ctx, hipStreamSynchronize(st));
-		levels.push_back(std::move(N));
+		else if (W.count(7)) CL_TRY(wave_rounds(E, lv, L, W, W.list(7), W.count(7), W.bytes(7), 0.0, false));   // (COLORD_HIP_NO_TEAM_ALIGN)
+		if (n_giant_redo) CL_TRY(wave_rounds(E, lv, L, W, giant.redo.p, n_giant_redo, 0.0, 0.0, false));
+		for (uint32_t cls = 0; cls < N_CLASSES; ++cls) ctx->gap_paths[cls] += W.count(cls);
+		ctx->gap_paths[8] += n_quad_redo; ctx->gap_paths[9] += n_giant_redo;
+		if (E.knobs.gap_debug) diag::level_line(ctx, lv, W.hb, n_quad_redo, n_giant_redo);
+		CL_TRY(small.wait(ctx));                                               // waits (side): classes 1 - 4 are through — every script of the level is written
+		if (E.knobs.gap_shapes) CL_TRY(diag::gap_shapes(ctx, lv, L, W.es_total));
+		CL_TRY(level_decisions(E, L, W, S));
+		if (lv >= max_rec || lv + 1 >= 10) { HIP_TRY(ctx, hipStreamSynchronize(E.st)); break; }   // waits (main): the last level's decisions, before its temporaries go
+		CL_TRY(level_spawn(E, W, S, levels));                                  // waits (main): 2 scan totals — candidates, frames; the end of the level
 	}
 	uint32_t herr = 0;
-	HIP_TRY(ctx, hipMemcpyAsync(&herr, err.p, 4, hipMemcpyDeviceToHost, st));
-	HIP_TRY(ctx, hipStreamSynchronize(st));
+	HIP_TRY(ctx, hipMemcpyAsync(&herr, err.p, 4, hipMemcpyDeviceToHost, E.st));
+	HIP_TRY(ctx, hipStreamSynchronize(E.st));                                // waits (main): the error word of all levels
 	if (herr) return cl_fail(ctx, CL_E_INVALID, "cl_encode_reads: inconsistent anchors");
-
-	TreeV T; memset(&T, 0, sizeof(T));
-	for (size_t i = 0; i < levels.size() && i < 10; ++i) T.lv[i] = levels[i]->view();
-	T.frame_of_read = frame_of_read.p;
-	// estimator (per reader pack), then tuples: sizes, offsets, bytes
-	DevBuf<uint32_t> base_counts; DEV_ALLOC(ctx, base_counts, 4ull * nr);
-	LAUNCHB(ctx, reads->total_bases / 4.0, k_read_base_counts, grid_for((uint64_t)nr * 64, 256), 256, A, has_n, nr, base_counts.p);
-	DevBuf<uint32_t> d_pb; DEV_ALLOC(ctx, d_pb, (uint64_t)n_packs + 1);
-	HIP_TRY(ctx, hipMemcpyAsync(d_pb.p, h_pack_bounds, ((uint64_t)n_packs + 1) * 4, hipMemcpyHostToDevice, st));
-	DevBuf<uint32_t> ev_cnt; DEV_ALLOC(ctx, ev_cnt, (uint64_t)nr + 1);
-	DevBuf<uint64_t> ev_off; DEV_ALLOC(ctx, ev_off, (uint64_t)nr + 1);
-	LAUNCH(ctx, k_pend_count, grid_for(nr, 64), 64, T, nr, ev_cnt.p);
-	uint64_t n_events = 0;
-	CL_TRY(dev_exclusive_scan_u64(ctx, ev_cnt.p, ev_off.p, nr, &n_events));
-	DevBuf<uint32_t> events; DEV_ALLOC(ctx, events, n_events + 1);
-	LAUNCH(ctx, k_pend_list, grid_for(nr, 64), 64, T, nr, (const uint64_t*)ev_off.p, events.p);
-	if (n_packs) LAUNCH(ctx, k_estimator, n_packs, 64, T, (const uint32_t*)d_pb.p, n_packs, (const uint32_t*)reads->lens.p, has_n, (const uint32_t*)base_counts.p, (const uint64_t*)ev_off.p, (const uint32_t*)events.p);
-	DevBuf<uint32_t> sizes; DEV_ALLOC(ctx, sizes, nr);
-	uint64_t total = 0;
-	{	// one wave per read, the lanes over the fragments of a frame (emit_wave.hpp)
-		LAUNCHB(ctx, reads->total_bases * 1.25, k_emit_count_wave, grid_for(nr, 4), 256, A, T, nr, AV.data, sizes.p, d_es_ntuples);
-		HIP_TRY(ctx, hipGetLastError());
-		CL_TRY(dev_exclusive_scan_u64(ctx, sizes.p, d_es_off, nr, &total));
-		*n_out = total;
-		if (total > cap || (total && !d_es)) return cl_fail(ctx, CL_E_CAPACITY, "cl_encode_reads: need " + std::to_string(total) + " bytes");
-		LAUNCHB(ctx, reads->total_bases * 1.25 + (double)total, k_emit_write_wave, grid_for(nr, 4), 256, A, T, nr, AV.data, (const uint64_t*)d_es_off, d_es);
-	}
-	LAUNCH(ctx, k_emit_plain, grid_for(nr, 4), 256, A, (const uint32_t*)reads->inv.p, has_n, (const uint32_t*)frame_of_read.p, nr, (const uint64_t*)d_es_off, d_es);
-	HIP_TRY(ctx, hipGetLastError());
-	HIP_TRY(ctx, hipStreamSynchronize(st));
+	CL_TRY(estimate_and_emit(E, reads, levels, frame_of_read.p, h_pack_bounds, n_packs, d_es, cap, d_es_off, d_es_ntuples, n_out));   // waits (main): 2 scan totals; the end of the call
 	cl_timing_collect(ctx);
 	return CL_OK;
 }

@@ -294,15 +294,16 @@ def plan_case(c):
     _, rev, _, anchors = cands[0]
     oriented = (3 - ref[::-1]).astype(np.uint8) if rev else ref
     gi = {"L": 0, "I": 1, "R": len(anchors)}[c["where"]]
-    classes = [0] * 8
+    classes, cells = [0] * 8, [0] * 8
     mine = None
     for g in range(len(anchors) + 1):
         geo = gap_geometry(anchors, len(read), len(ref), g)
         cls, rows, cols = gap_class(geo["kind"], geo["use"], geo["ne"])
         classes[cls] += 1
+        cells[cls] += rows * cols
         if g == gi:
             mine = dict(geo, cls=cls, rows=rows, cols=cols)
-    P = dict(name=c["name"], rev=int(rev), anchors=anchors, classes=classes, **mine)
+    P = dict(name=c["name"], rev=int(rev), anchors=anchors, classes=classes, cells=cells, **mine)
     rp, ep = oriented[P["cur_ref"]:P["cur_ref"] + P["nr"]], read[P["cur_enc"]:P["cur_enc"] + P["ne"]]
     P["ref_part"], P["enc_part"] = rp, ep
     es, dist = O.gap_script(rp, ep, WHERE_CODE[c["where"]] if len(anchors) else 1)
@@ -351,6 +352,11 @@ def totals(plans):
     """what cl_ctx_gap_paths must report for one call over these cases: gaps per class, quad -> wave"""
     classes = [sum(p["classes"][k] for p in plans) for k in range(8)]
     return classes, sum(p["quad_redo"] for p in plans)
+
+
+def total_cells(plans):
+    """DP cells (rows x columns of every gap) per class of one call over these cases: what a timed context books on the aligners' launches"""
+    return [sum(p["cells"][k] for p in plans) for k in range(8)]
 
 
 def describe(c, p):

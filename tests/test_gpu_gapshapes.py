@@ -68,6 +68,37 @@ def test_constructed_gaps_equal_oracle(ctx, group, decisions):
     run_group(ctx, G.group(group), decisions)
 
 
+CLASS_KERNELS = {1: "k_align_small<1>", 2: "k_align_small<2>", 3: "k_align_small<3>", 4: "k_align_small<4>", 5: "k_align_quad_rows<false>", 6: "k_align_wave", 7: "k_giant_stage"}
+
+
+@pytest.mark.parametrize("group", ["small", "quad", "wave", "giant"])
+def test_timed_call_books_every_class_once(group):
+    """The timing branch of the encoder's driver (what the benchmark reports from): with every script accepted there is no second level, so
+    the DP cells a timed call books per aligner are level 0's — rows x columns of every gap of the class, booked once, on the class's own
+    kernel.  The wave kernel's redo launches book nothing, so a class-5 gap it redoes stays booked on class 5 only."""
+    from colord_amd.device import Context
+    cases = G.group(group)
+    plans = G.plan(cases)
+    classes, quad_to_wave = G.totals(plans)
+    cells = G.total_cells(plans)
+    c = Context(0, timing=True)
+    try:
+        c.kernel_times(); c.acc.clear()                                # (clears)
+        run_group(c, cases, G.ACCEPT_ALL)                              # (anchors, paths, bytes: the same checks with timing on)
+        times = {k: list(v) for k, v in c.acc.items()}                 # (every checked API call of a timing context moves its kernel times into acc)
+        for k, v in c.kernel_times().items():
+            times[k] = [a + b for a, b in zip(times.get(k, [0.0, 0, 0.0, 0.0]), v)]
+        for cls, name in CLASS_KERNELS.items():
+            _, launches, _, booked = times.get(name, (0.0, 0, 0.0, 0.0))
+            print(f"class {cls} {name}: {classes[cls]} gaps, {cells[cls]} cells planned; {launches} launches, {booked:.0f} cells booked")
+            assert booked == cells[cls], f"DP cells booked on {name}"
+            # (the wave kernel also runs what the four-per-wave kernel hands back; run_group has asserted that the giants hand nothing back)
+            wanted = classes[cls] > 0 or (cls == 6 and quad_to_wave > 0)
+            assert (launches >= 1) if wanted else (launches == 0), f"launches of {name} for {classes[cls]} gaps of class {cls}"
+    finally:
+        c.close()
+
+
 @pytest.mark.parametrize("decisions", [G.ACCEPT_ALL, G.PRESET], ids=["accept_all", "preset"])
 def test_giant_thresholds_equal_oracle(ctx, decisions):
     """4096 / 4097 rows (GIANT_ROWS: a second tile of ONE row), 65 x 8065 / 8066 block-columns (GIANT_WORK), rows / 8 against the columns:
