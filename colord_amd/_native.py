@@ -77,6 +77,11 @@ class KSpec(C.Structure):
     as_dict = Report.as_dict
 
 
+class Overlap(C.Structure):
+    """cl_overlap: one visit of a read's edit script on one reference read that holds an aligned column; twelve little-endian uint32."""
+    _fields_ = [(k, C.c_uint32) for k in ("q", "t", "qlen", "tlen", "qs", "qe", "ts", "te", "matches", "subst", "anchor_bases", "flags")]
+
+
 _P = C.c_void_p
 class CompressParams(C.Structure):
     _fields_ = [("k", C.c_uint32), ("f", C.c_uint32), ("ci", C.c_uint32), ("cs", C.c_uint32), ("c", C.c_uint32),
@@ -149,6 +154,12 @@ _SIG = {
     "cl_ctx_set_kmer_spectrum": (None, [_P, C.c_int]),
     "cl_ctx_kmer_spectrum": (C.c_int32, [_P, C.POINTER(KSpec)]),
     "cl_compressor_kmer_spectrum": (C.c_int32, [_P, C.POINTER(KSpec)]),
+    "cl_overlaps_of": (C.c_int32, [_P, _P, _P, _P, C.c_uint32, C.c_uint64, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cl_overlaps_host": (C.c_int32, [_P, _P, C.c_uint32, _P, _P, C.c_uint64, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint32)]),
+    "cl_ctx_set_overlaps": (None, [_P, C.c_int]),
+    "cl_ctx_overlaps": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cl_compressor_overlaps": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cl_digest_bases": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(Digest)]),
     "cl_digest_quals": (C.c_int32, [_P, C.POINTER(QualParams), _P, _P, _P, C.c_uint64, C.POINTER(Digest)]),
     "cl_digest_bases_host": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(Digest)]),

@@ -205,7 +205,8 @@ int run_compress(int argc, char** argv)
 	if (O.report) cl_ctx_set_report(ctx, 1);
 	if (O.edit_profile) cl_ctx_set_edit_profile(ctx, 1);
 	if (O.kmer_spectrum) cl_ctx_set_kmer_spectrum(ctx, 1);
-	std::vector<uint64_t> report_lens;                          // --report: every read length, as the reader hands the reads over in pass 1 (N50 / N90)
+	if (O.overlaps) cl_ctx_set_overlaps(ctx, 1);
+	std::vector<uint64_t> report_lens;                         // --report: every read length, as the reader hands the reads over in pass 1 (N50 / N90)
 	ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, nullptr, estimated_bases(R), &cmp), "cl_compressor_create");
 	if (O.qual_domain_symbols)
 	{
@@ -350,6 +351,16 @@ int run_compress(int argc, char** argv)
 		KSpecSet K;
 		ck(ctx, cl_compressor_kmer_spectrum(cmp, K.s.get()), "cl_compressor_kmer_spectrum");
 		add_kspec(ar, K, prm.cp, GM.on, 1, ks.tot_kmers, ks.n_unique);
+	}
+	if (O.overlaps)
+	{
+		OverlapSet V; uint64_t nv = 0;
+		const cl_status s = cl_compressor_overlaps(cmp, nullptr, 0, &nv);
+		if (s != CL_OK && s != CL_E_CAPACITY) ck(ctx, s, "cl_compressor_overlaps");
+		V.recs.resize(nv);
+		if (nv) ck(ctx, cl_compressor_overlaps(cmp, V.recs.data(), nv, &nv), "cl_compressor_overlaps");
+		add_overlaps(ar, V, n);
+		if (O.verbose) fprintf(stderr, "# overlaps: %llu records\n", (unsigned long long)nv);
 	}
 	if (O.qual_domain_symbols)
 	{

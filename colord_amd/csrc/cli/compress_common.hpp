@@ -9,6 +9,7 @@
 #include "digest_stream.hpp"
 #include "report_stream.hpp"
 #include "edits_stream.hpp"
+#include "overlaps_stream.hpp"
 #include "kspec_stream.hpp"
 #include <ctime>
 #include <mutex>
@@ -339,6 +340,14 @@ inline void add_kspec(ArchiveWriter& ar, KSpecSet& S, const cl_compress_params& 
 	S.flags = genome ? 1u : 0u; S.k = cp.k; S.f = cp.f; S.ci = cp.ci; S.cs = cp.cs; S.sets = sets;
 	const std::vector<uint8_t> b = S.pack();
 	ar.add(ar.reg("hipkmers"), b.data(), b.size(), 0);
+}
+// --overlaps: the `hipoverlaps` stream (overlaps_stream.hpp), before finish_archive: the records the compressor's context and its lanes kept, in
+// input order; every record must name reads of the input
+inline void add_overlaps(ArchiveWriter& ar, const OverlapSet& S, uint64_t n_reads)
+{
+	for (const cl_overlap& o : S.recs) if (o.q >= n_reads || o.t >= n_reads) die("internal: an overlap record names a read outside the input");
+	const std::vector<uint8_t> b = S.pack();
+	ar.add(ar.reg("hipoverlaps"), b.data(), b.size(), 0);
 }
 // --report with a *-fix mode: the -D values must be qualities the report can index
 inline void check_report_options(const Options& O, bool with_qual)

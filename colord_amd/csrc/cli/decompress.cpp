@@ -5,6 +5,7 @@
 // against it while it is decoded; `check` decodes without writing and prints the digests.
 #include "reader.hpp"
 #include "edits_stream.hpp"
+#include "overlaps_stream.hpp"
 #include "kspec_stream.hpp"
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -109,14 +110,28 @@ struct DeviceQualDecoder {
 
 int run_info(int argc, char** argv)
 {
-	bool want_report = false, want_edits = false, want_kspec = false, json = false; std::vector<std::string> pos;
+	bool want_report = false, want_edits = false, want_kspec = false, want_overlaps = false, names = false, json = false; std::vector<std::string> pos;
+	uint64_t min_block = 0; bool has_min_block = false;
 	for (int i = 2; i < argc; ++i)
 	{
 		const std::string a = argv[i];
-		if (a == "--report") want_report = true; else if (a == "--edit-profile") want_edits = true; else if (a == "--kmer-spectrum") want_kspec = true; else if (a == "--json") json = true; else pos.push_back(a);
+		if (a == "--overlaps") want_overlaps = true;
+		else if (a == "--names") names = true;
+		else if (a == "--min-block")
+		{
+			char* end = nullptr;
+			if (i + 1 >= argc || !isdigit((unsigned char)argv[i + 1][0])) die("option --min-block needs a number");
+			min_block = strtoull(argv[++i], &end, 10); has_min_block = true;
+			if (*end) die("option --min-block needs a number");
+		}
+		else if (a == "--report") want_report = true; else if (a == "--edit-profile") want_edits = true; else if (a == "--kmer-spectrum") want_kspec = true; else if (a == "--json") json = true; else pos.push_back(a);
 	}
 	const int wanted = (want_report ? 1 : 0) + (want_edits ? 1 : 0) + (want_kspec ? 1 : 0);
-	if (pos.size() != 1 || (json && !wanted) || wanted > 1) { fprintf(stderr, "usage: colord_hip info [--report [--json]] [--edit-profile [--json]] [--kmer-spectrum [--json]] archive.colord\n"); return 1; }
+	if (pos.size() != 1 || (json && !wanted) || wanted + (want_overlaps ? 1 : 0) > 1 || ((names || has_min_block) && !want_overlaps))
+	{
+		fprintf(stderr, "usage: colord_hip info [--report [--json]] [--edit-profile [--json]] [--kmer-spectrum [--json]] archive.colord\n       colord_hip info --overlaps [--min-block N] [--names] archive.colord\n");
+		return 1;
+	}
 	const std::string& path = pos[0];
 	ArchiveReader ar;
 	if (!ar.open(path)) die("cannot open archive: " + path);
@@ -136,6 +151,28 @@ int run_info(int argc, char** argv)
 		if (have == 0) die("no edit profile is stored in this archive (written without --edit-profile)");
 		if (have < 0) die("the archive's `hipedits` stream is not one this build reads");
 		if (json) print_edits_json(stdout, E); else print_edits(stdout, E);
+		return 0;
+	}
+	if (want_overlaps)
+	{	// the stored overlap records as PAF, on stdout: `dna` and `qual` are not decoded; --names decodes the `header` stream on the host
+		ar.close();
+		OverlapSet V; const int have = read_hipoverlaps(path, V);
+		if (have == 0) die("no overlaps are stored in this archive (written without --overlaps)");
+		if (have < 0) die("the archive's `hipoverlaps` stream is not one this build reads");
+		std::vector<std::string> ids;
+		if (names)
+		{
+			HeaderCache H; H.decode_all(path);
+			if (!H.err.empty()) die("--names: " + H.err);
+			for (size_t i = 0; i + 1 < H.off.size(); ++i)
+			{	// a read's name: its id up to the first blank, or its index where no id is stored (-i none)
+				std::string id((const char*)H.ids.data() + H.off[i], (const char*)H.ids.data() + H.off[i + 1]);
+				const size_t cut = id.find_first_of(" \t");
+				if (cut != std::string::npos) id.resize(cut);
+				ids.push_back(id.empty() ? std::to_string(i) : id);
+			}
+		}
+		if (!print_paf(stdout, V, min_block, names ? &ids : nullptr)) die("the archive's `hipoverlaps` stream names a read the `header` stream does not hold");
 		return 0;
 	}
 	if (want_kspec)
@@ -172,6 +209,10 @@ int run_info(int argc, char** argv)
 		fprintf(stderr, "k-mer spectrum: %llu sampled k-mers (1 in %u), %llu distinct, highest count %llu (`colord_hip info --kmer-spectrum [--json]` prints it)\n", (unsigned long long)ksp.s->kmers, ksp.f, (unsigned long long)ksp.s->distinct,
 			(unsigned long long)ksp.s->max_count);
 	else if (have < 0) fprintf(stderr, "k-mer spectrum: a `hipkmers` stream this build cannot read\n");
+	OverlapSet ovl;
+	if (const int have = read_hipoverlaps(path, ovl); have > 0)
+		fprintf(stderr, "overlaps: %llu records of reads against reference reads (`colord_hip info --overlaps [--min-block N] [--names]` prints them as PAF)\n", (unsigned long long)ovl.recs.size());
+	else if (have < 0) fprintf(stderr, "overlaps: a `hipoverlaps` stream this build cannot read\n");
 	return 0;
 }
 

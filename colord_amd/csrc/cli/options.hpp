@@ -42,6 +42,7 @@ struct Options {
 	bool report = false;                            // --report: the content report of the input (cl_ctx_set_report) in a `hipreport` stream
 	bool edit_profile = false;                      // --edit-profile: the edit-operation profile of the tuple streams (cl_ctx_set_edit_profile) in a `hipedits` stream
 	bool kmer_spectrum = false;                     // --kmer-spectrum: the count spectrum of the k-mers pass 1 counted (cl_ctx_set_kmer_spectrum) in a `hipkmers` stream
+	bool overlaps = false;                          // --overlaps: the read-to-read overlaps the edit scripts hold (cl_ctx_set_overlaps) in a `hipoverlaps` stream
 	uint64_t qual_domain_symbols = 0;               // --qual-domain-symbols N: the quality models start afresh about every N symbols (cl_compressor_set_qual_domain_symbols; stream `hipqdomains`)
 	int gpus = 1; std::vector<int> gpu_list; std::string transport = "rccl";   // --gpus N [--gpu-list a,b,..] [--transport rccl|host]: reads sharded over N GPUs (run_compress_multi)
 	Preset P{}; QDef qd;                            // resolved by parse_options: the preset of source and priority with the options laid over it, the quality thresholds / representatives
@@ -52,7 +53,7 @@ inline void usage()
 {
 	fprintf(stderr,
 		"usage: colord_hip compress-ont|compress-pbhifi|compress-pbraw [options] input.fastq|fasta[.gz] output.colord\n"
-		"       colord_hip decompress [--ignore-digest] [--gpu N] archive.colord output.fastq\n       colord_hip check [--gpu N] archive.colord\n       colord_hip info [--report [--json]] [--edit-profile [--json]] [--kmer-spectrum [--json]] archive.colord\n"
+		"       colord_hip decompress [--ignore-digest] [--gpu N] archive.colord output.fastq\n       colord_hip check [--gpu N] archive.colord\n       colord_hip info [--report [--json]] [--edit-profile [--json]] [--kmer-spectrum [--json]] archive.colord\n       colord_hip info --overlaps [--min-block N] [--names] archive.colord\n"
 		"options (as the reference, arg_parse.cpp:455-640):\n"
 		"  -p,--priority ratio|balanced|memory   -k,--kmer-len K with -a,--anchor-len A (both or none)\n"
 		"  -q,--qual org|none|avg|2-fix|4-fix|5-fix|2-avg|4-avg|5-avg   -T,--qual-thresholds a,b,..   -D,--qual-values a,b,..\n"
@@ -108,6 +109,16 @@ inline void usage()
 		"                     no estimate).  `decompress` / `check` do not recompute it.  Cost: one pass over 4 bytes per distinct sampled k-mer;\n"
 		"                     measured on an MI355X, 400 Mbases of synthetic ONT reads (33.3 M sampled k-mers, 27.6 M distinct): k_run_spectrum 0.077 ms of kernel time next to 2.61 ms of all kernels of\n"
 		"                     the same count, 0.10 ms of wall time on 2.90 ms; at 5 Gbases in the benchmark about 1 ms in a pass of 1.9 s, inside the run-to-run spread (DESIGN.md 9)\n"
+		"  --overlaps         the read-to-read overlaps that the edit scripts hold are stored in the archive (stream `hipoverlaps`, 48 bytes per record; the reference's decompressor ignores it):\n"
+		"                     one record per stretch of a read's edit script on ONE reference read that holds an aligned column — where on the read, where on the reference read in its\n"
+		"                     forward coordinates, strand, matches, substitutions, anchor bases — made on the device right behind the edit scripts.  `colord_hip info --overlaps\n"
+		"                     [--min-block N] [--names] archive` prints them as PAF without decoding `dna` or `qual` (tags mm:i: substitutions, an:i: anchor bases, tp:A:P the main reference,\n"
+		"                     tp:A:S an alternative; names are input indices unless --names decodes the `header` stream).  THIS IS A READ AGAINST EARLIER READS, WHICH CARRY ERRORS OF\n"
+		"                     THEIR OWN, AND IT LISTS OVERLAPS WITH REFERENCE READS ONLY: about a tenth of the reads with the sparse acceptor (-R sparse), all of them with -R all.\n"
+		"                     `decompress` / `check` ignore the stream.  Works with --stream-input, --part-symbols, --chunk-bases.  Not with --gpus > 1, --domains > 1 or -G.\n"
+		"                     Cost: one pass over the tuple bytes per chunk to count and one to fill; measured on an MI355X, 1 Gbase of synthetic ONT reads (64 156 reads): 12.2 + 12.9 ms of kernel\n"
+		"                     time next to 23.5 ms of --edit-profile and 962 ms of all kernels; 1.77 s from file to archive against 1.69 s without the option, inside the spread of three runs;\n"
+		"                     88 989 records, 4.3 MB, 1.1 percent of the archive (DESIGN.md 9)\n"
 		"  --qual-domain-symbols N   model domains of the QUALITY stream alone: its adaptive models start afresh at the first part boundary at which a domain holds N coded\n"
 		"                     symbols, and the starts are recorded (stream `hipqdomains`).  `colord_hip decompress --gpu N` / `check --gpu N` then decode the domains side by\n"
 		"                     side on the device, one lane each; without --gpu they decode on the host as one chain that starts afresh at every domain.  The k-mer set, the\n"
@@ -176,6 +187,7 @@ inline Options parse_options(int argc, char** argv)
 		else if (a == "--report") O.report = true;
 		else if (a == "--edit-profile") O.edit_profile = true;
 		else if (a == "--kmer-spectrum") O.kmer_spectrum = true;
+		else if (a == "--overlaps") O.overlaps = true;
 		else if (a == "--parse-threads") { O.parse_threads = atoi(need(i).c_str()); if (O.parse_threads < 1 || O.parse_threads > 256) die("--parse-threads must be in [1, 256]"); }
 		else if (a == "-h" || a == "--help") { usage(); exit(0); }
 		else if (!a.empty() && a[0] == '-' && a.size() > 1) die("unknown option " + a);
@@ -208,6 +220,12 @@ inline Options parse_options(int argc, char** argv)
 		if (O.gpus > 1) die("--qual-domain-symbols is not available with --gpus > 1 (every GPU is a model domain already)");
 		if (O.domains > 1) die("--qual-domain-symbols is not available with --domains > 1");
 		if (P.qual_mode == 8) die("--qual-domain-symbols needs a coded quality stream: not with -q none (the default of compress-pbraw)");
+	}
+	if (O.overlaps)
+	{	// a record names reads of the input: every reference id must be one of them, in ONE set of reference reads
+		if (O.gpus > 1) die("--overlaps is not available with --gpus > 1 (the ranks' reference ids are not translated to reads of the input yet)");
+		if (O.domains > 1) die("--overlaps is not available with --domains > 1 (every domain has its own reference reads)");
+		if (!O.genome.empty()) die("--overlaps is not available with -G (the pseudo reads of a reference genome are no reads of the input)");
 	}
 	return O;
 }

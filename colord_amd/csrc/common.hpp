@@ -357,6 +357,9 @@ struct cl_ctx {
 	mutable std::mutex edits_mu;
 	bool kmer_spectrum = false;                  // cl_ctx_set_kmer_spectrum: count_range (kmer.hip) adds the count spectrum of every key range it counts (kspec.hip)
 	cl_kspec* kspec_acc = nullptr;               // the total so far (owner thread only); freed with the context
+	bool overlaps = false;                       // cl_ctx_set_overlaps: tuple_streams (pass_steps.hpp) keeps the overlap records of every batch it makes (overlaps.hip)
+	std::map<uint64_t, std::vector<cl_overlap>> overlap_recs;   // the records of the batches made on THIS context by the batch's first read (under overlaps_mu: cl_ctx_overlaps merges the encode lanes')
+	mutable std::mutex overlaps_mu;
 	uint64_t gap_paths[11] = { 0 };              // cl_ctx_gap_paths: the last cl_encode_reads' gaps per size class 0..7, quad -> wave, giant -> wave, wave-pool redo rounds (owner thread only)
 	std::map<std::string, KernelTime> times;     // per-kernel accumulated HIP-event time of the last API call
 	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;

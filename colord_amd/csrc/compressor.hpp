@@ -68,6 +68,7 @@ struct cl_compressor {
 	Grow<uint32_t> pair_ids, pair_refs;
 	std::vector<DevBuf<uint32_t>> bounds;           // per chunk: n_reads + 1, reference reads before each read
 	cl_reads* refs = nullptr; cl_index* index = nullptr; uint32_t ref_base = 0, n_refs_total = 0;
+	DevBuf<uint32_t> ref_read;                      // cl_ctx_set_overlaps: reference id -> index of that read in the input (n_refs_total entries), made in refs_finish
 	cl_dna_coder* dna = nullptr; cl_qual_coder* qual = nullptr;
 	uint64_t qual_domain_symbols = 0;               // cl_compressor_set_qual_domain_symbols: handed to the quality coder when it is created
 	// pass 2b

@@ -48,7 +48,14 @@ extern "C" cl_status cl_compress_shard(cl_ctx* ctx, const cl_compress_params* P,
 	info->n_refs = refs.p->n_reads;
 	// a5 candidates (every read against the reference reads before it: the index's own ranks) ... a12 tuple streams; then the coders
 	TupleStreams ts;
-	CL_TRY(tuple_streams(ctx, P, lists, index, refs, reads, cl_index_ref_rank(index), h_pack_bounds, n_packs, ts));
+	DevBuf<uint32_t> ref_read;                                 // cl_ctx_set_overlaps: reference id -> read index of this one shard, from the index's ranks
+	if (ctx->overlaps && refs.p->n_reads)
+	{
+		DEV_ALLOC(ctx, ref_read, refs.p->n_reads);
+		HIP_TRY(ctx, hipMemsetAsync(ref_read.p, 0xff, (uint64_t)refs.p->n_reads * 4, cl_launch_stream(ctx)));
+		CL_TRY(overlaps_ref_reads(ctx, cl_index_ref_rank(index), n, 0, ref_read.p, refs.p->n_reads));
+	}
+	CL_TRY(tuple_streams(ctx, P, lists, index, refs, reads, cl_index_ref_rank(index), h_pack_bounds, n_packs, 0, ref_read.p, ref_read.p ? refs.p->n_reads : 0u, ts));
 	info->n_anchors = ts.n_anchors; info->tuple_bytes = ts.es_bytes;
 	return coder.code(refs, ts);
 }

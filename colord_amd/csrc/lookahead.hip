@@ -36,6 +36,7 @@ template<class Work> static cl_status work_on(cl_compressor* c, cl_ctx* ctx, Wor
 	ctx->timing = c->ctx->timing;
 	ctx->verify = c->ctx->verify;
 	ctx->edit_profile = c->ctx->edit_profile;
+	ctx->overlaps = c->ctx->overlaps;
 	const cl_status s = work();
 	cl_timing_collect(ctx);
 	return s;

@@ -68,6 +68,11 @@ cl_status report_chunk(cl_ctx* ctx, const cl_reads* reads, const cl_qual_params*
 cl_status edit_profile_chunk(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads);
 // kspec.hip (cl_ctx_set_kmer_spectrum): the count spectrum of one counted key range — the run starts of its n sorted keys — added to the context's total
 cl_status kmer_spectrum_range(cl_ctx* ctx, const uint32_t* d_head_pos, uint64_t n_heads, uint64_t n);
+// overlaps.hip (cl_ctx_set_overlaps): the overlap records of a batch of tuple streams whose first read is read `first_read` of the input, kept on the
+// host by the context that made them; d_ref_read (n_ref_read entries, or null): reference id -> input index
+cl_status overlaps_chunk(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, const uint32_t* d_ref_read, uint32_t n_ref_read);
+// ... and that table's entries of one chunk: read i (input index first_read + i) is reference d_bounds[i] iff d_bounds[i + 1] > d_bounds[i] (n + 1 bounds)
+cl_status overlaps_ref_reads(cl_ctx* ctx, const uint32_t* d_bounds, uint32_t n, uint32_t first_read, uint32_t* d_ref_read, uint32_t n_ref_read);
 const cl_qual_params* cl_qual_coder_params(const cl_qual_coder* q);     // qual.hip: the parameters the coder was created with
 
 // the DNA coder's state-independent half ahead of time (dna.hip): lookahead.hip walks the NEXT chunk's tuples from the hook that

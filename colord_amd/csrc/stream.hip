@@ -327,6 +327,14 @@ extern "C" cl_status cl_compressor_refs_finish(cl_compressor* c)
 		c->ref_pieces.clear();
 	}
 	c->ref_base = 0; c->n_refs_total = nr;
+	if (ctx->overlaps)
+	{	// reference id -> read index, once, from the chunks' bounds (one rank, no pseudo reads: refused below otherwise)
+		if (c->world > 1 || c->n_pseudo) return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_ctx_set_overlaps: not with reads sharded over ranks or the pseudo reads of a reference genome (their reference ids are not reads of this input)");
+		if (nr) { DEV_ALLOC(ctx, c->ref_read, nr); HIP_TRY(ctx, hipMemsetAsync(c->ref_read.p, 0xff, (uint64_t)nr * 4, cl_launch_stream(ctx))); }
+		uint64_t g = 0;
+		for (size_t i = 0; i < c->bounds.size(); ++i) { if (nr) CL_TRY(overlaps_ref_reads(ctx, c->bounds[i].p, c->chunk_reads[i], (uint32_t)g, c->ref_read.p, nr)); g += c->chunk_reads[i]; }
+		HIP_TRY(ctx, hipStreamSynchronize(cl_launch_stream(ctx)));
+	}
 	uint64_t n_pairs = c->pair_ids.n;
 	if (c->world > 1) CL_TRY(gather_refs(c, pk, iv, ln, words, nr, n_pairs));
 	CL_TRY(cl_reads_from_arena(ctx, pk.p, iv.p, ln.p, nr, &c->refs));
@@ -352,7 +360,8 @@ cl_status compressor_tuple_streams(cl_compressor* c, cl_ctx* ctx, size_t idx, co
 {
 	Handle<cl_kmer_lists, cl_kmer_lists_free> lists;            // a4: accepted k-mers per read
 	CL_TRY(cl_accepted_kmers(ctx, c->kset, reads, c->P.k, c->P.f, lists.out()));
-	return tuple_streams(ctx, &c->P, lists, c->index, c->refs, reads, c->bounds[idx].p, h_pack_bounds, n_packs, out);
+	uint64_t g = c->first_read; for (size_t i = 0; i < idx; ++i) g += c->chunk_reads[i];      // the chunk's first read in the whole input
+	return tuple_streams(ctx, &c->P, lists, c->index, c->refs, reads, c->bounds[idx].p, h_pack_bounds, n_packs, g, c->ref_read.p, c->ref_read.p ? c->n_refs_total : 0u, out);
 }
 
 extern "C" cl_status cl_compressor_encode(cl_compressor* c, const cl_reads* reads, const uint8_t* d_quals, const uint64_t* d_base_off,
@@ -445,6 +454,10 @@ extern "C" cl_status cl_compressor_report(const cl_compressor* c, cl_report* out
 extern "C" cl_status cl_compressor_edit_profile(const cl_compressor* c, cl_edits* out)
 {
 	return c ? cl_ctx_edit_profile(c->ctx, out) : CL_E_INVALID;
+}
+extern "C" cl_status cl_compressor_overlaps(const cl_compressor* c, cl_overlap* h_out, uint64_t cap, uint64_t* n_out)
+{
+	return c ? cl_ctx_overlaps(c->ctx, h_out, cap, n_out) : CL_E_INVALID;
 }
 extern "C" cl_status cl_compressor_kmer_spectrum(const cl_compressor* c, cl_kspec* out)
 {

@@ -57,7 +57,8 @@ class _OrderedLib:
                   "cl_qual_coder_domains", "cl_compressor_qual_domains", "cl_ctx_gap_paths",
                   "cl_report_clear", "cl_report_add", "cl_report_bases_host", "cl_report_quals_host", "cl_report_values_host", "cl_ctx_set_report", "cl_ctx_report", "cl_compressor_report",
                   "cl_edits_clear", "cl_edits_add", "cl_edit_profile_host", "cl_edit_profile_error", "cl_ctx_set_edit_profile", "cl_ctx_edit_profile", "cl_compressor_edit_profile",
-                  "cl_kspec_clear", "cl_kspec_add", "cl_ctx_set_kmer_spectrum", "cl_ctx_kmer_spectrum", "cl_compressor_kmer_spectrum")
+                  "cl_kspec_clear", "cl_kspec_add", "cl_ctx_set_kmer_spectrum", "cl_ctx_kmer_spectrum", "cl_compressor_kmer_spectrum",
+                  "cl_overlaps_host", "cl_ctx_set_overlaps", "cl_ctx_overlaps", "cl_compressor_overlaps")
 
     def __init__(self, lib, device):
         self._lib, self._device, self._cache = lib, device, {}
@@ -215,6 +216,39 @@ class Context:
         n = max(es_off.numel() - 1, 0)
         _check(self, self.lib.cl_edit_profile(self.h, refs.h, es.data_ptr() if es.numel() else None, es_off.data_ptr() if n else None, n, flush_bytes, max_blocks, C.byref(acc)))
         return acc
+
+    def set_overlaps(self, on: bool = True):
+        """cl_ctx_set_overlaps: every batch of tuple streams made on this context or by a lane of its compressors leaves its overlap records
+        (dropped when switched on)."""
+        self.lib.cl_ctx_set_overlaps(self.h, int(bool(on)))
+
+    def overlaps(self) -> np.ndarray:
+        """cl_ctx_overlaps: the records so far of this context and its compressor's encode lanes in input order, (n, 12) uint32 in the field
+        order of cl_overlap."""
+        return _overlap_records(self.lib.cl_ctx_overlaps, self.h)
+
+    def overlaps_of(self, refs: "Reads", es: torch.Tensor, es_off: torch.Tensor, first_read: int = 0, ref_read: "torch.Tensor | None" = None, max_blocks: int = 0,
+                    cap: "int | None" = None) -> torch.Tensor:
+        """cl_overlaps_of: the overlap records of the tuple streams es / es_off (n + 1 byte offsets) against the arena refs, (n, 12) int32 on the
+        device (the bits of uint32, field order of cl_overlap).  ref_read: reference id -> input index (a 4-byte dtype on the device).  With cap
+        the call is made once with room for cap records (CL_E_CAPACITY raises); without, the need is asked for first.  A malformed stream
+        raises (CL_E_INVALID, the text names the first such read)."""
+        es, es_off = es.contiguous(), es_off.contiguous()
+        n = max(es_off.numel() - 1, 0)
+        if ref_read is not None:
+            assert ref_read.element_size() == 4
+            ref_read = ref_read.contiguous()
+        args = (self.h, refs.h, es.data_ptr() if es.numel() else None, es_off.data_ptr() if n else None, n, first_read,
+                ref_read.data_ptr() if ref_read is not None and ref_read.numel() else None, ref_read.numel() if ref_read is not None else 0, max_blocks)
+        need = C.c_uint64(0)
+        if cap is None:
+            st = self.lib.cl_overlaps_of(*args, None, 0, C.byref(need))
+            if st not in (N.CL_OK, N.CL_E_CAPACITY):
+                _check(self, st)
+            cap = need.value
+        out = torch.empty((cap, 12), dtype=torch.int32, device=self.device)
+        _check(self, self.lib.cl_overlaps_of(*args, out.data_ptr() if cap else None, cap, C.byref(need)))
+        return out[:need.value]
 
     def set_kmer_spectrum(self, on: bool = True):
         """cl_ctx_set_kmer_spectrum: every count_filter() on this context, and the pass 1 of its compressors, adds the count spectrum of the
@@ -778,9 +812,25 @@ def _domain_list(ctx, fn, h):
     return [int(x) for x in out[:n.value]]
 
 
+def _overlap_records(fn, h) -> np.ndarray:
+    """the records a context or a compressor keeps (cl_ctx_overlaps / cl_compressor_overlaps): the need first, then that many"""
+    n = C.c_uint64(0)
+    st = fn(h, None, 0, C.byref(n))
+    if st not in (N.CL_OK, N.CL_E_CAPACITY):
+        _check(None, st)
+    out = np.zeros((n.value, 12), np.uint32)
+    if n.value:
+        _check(None, fn(h, out.ctypes.data, n.value, C.byref(n)))
+    return out[:n.value]
+
+
 class Compressor(_Obj):
     """cl_compressor: pass 1 / reference listing / pass 2 over the chunks of an input (csrc/stream.hip)."""
     _free = "cl_compressor_free"
+
+    def overlaps(self) -> np.ndarray:
+        """cl_compressor_overlaps: the overlap records of the chunks whose tuple streams are made (Context.set_overlaps), in input order."""
+        return _overlap_records(self.ctx.lib.cl_compressor_overlaps, self.h)
 
     def __init__(self, ctx, h, qual_ctx, has_qual, exchange):
         super().__init__(ctx, h)

@@ -510,6 +510,47 @@ cl_status cl_kmer_spectrum_heads(cl_ctx* ctx, const uint32_t* d_head_pos, uint64
 void cl_ctx_set_kmer_spectrum(cl_ctx* ctx, int on);
 cl_status cl_ctx_kmer_spectrum(const cl_ctx* ctx, cl_kspec* out);
 
+/* ---- read-to-read overlaps (no counterpart in the reference) — what the edit scripts aligned, per read ---------------- */
+/* One record per VISIT of a read's tuple stream that holds an aligned column.  A visit is a stretch of tuples on one reference read:
+ * it opens behind the start-es tuple and behind every alt-id / main-ref tuple; every alt-id and main-ref tuple closes the open one (a
+ * main-ref met while on the main reference too), and so does the stream's end.  The walk is that of the edit profile with one more
+ * cursor, the read position: ins read +1; del reference +1; match / subst both +1 (an aligned column); anchor v both +v (aligned iff
+ * v > 0); skip v reference +v, the entry skip behind an alt-id included.  Plain reads and visits of insertions, deletions and skips
+ * only give no record.  LIKE THE PROFILE THIS IS A READ AGAINST EARLIER READS, WHICH CARRY ERRORS OF THEIR OWN, and it lists overlaps
+ * with REFERENCE reads only: about a tenth of the reads with the sparse acceptor, all of them otherwise.
+ *   q               index of the read in the input
+ *   t               the reference id as the stream has it, or the input index of that read where a translation table is given
+ *   qlen, tlen      bases the stream produces; length of the reference read
+ *   qs, qe          the read's interval: in front of the visit's first aligned column, behind its last (leading and trailing
+ *                   insertions, deletions and skips do not count)
+ *   ts, te          the same on the reference, in the reference's FORWARD coordinates (mirrored when it is taken reversed)
+ *   matches         match tuples plus anchor lengths of the visit;  subst: its subst tuples;  anchor_bases: its anchor lengths
+ *   flags           bit 0: the reference is taken reversed (an alternative's first appearance in the read decides);  bit 1: the main reference
+ * The alignment block length is not stored: (qe - qs) + (te - ts) - matches - subst.  Records of a read are in visit order. */
+typedef struct cl_overlap { uint32_t q, t, qlen, tlen, qs, qe, ts, te, matches, subst, anchor_bases, flags; } cl_overlap;
+/* The records of n_reads tuple streams (d_es / d_es_off as cl_encode_reads writes them) against the arena `refs`, reads in order, into
+ * d_out (device, cap records); read r of the batch is read first_read + r of the input.  d_ref_read (device, n_ref_read entries; or
+ * null): reference id -> input index, for `t`; an id at or past n_ref_read is then malformed (a reference id outside).  On the device
+ * (k_overlap_walk): a wave per read, the stream 64 bytes per step, persistent blocks of four waves (max_blocks bounds the grid, 0: four
+ * per CU; it changes no result); one pass counts, a prefix sum places, the same kernel body fills.  *n_out = the records.  cap too
+ * small (or d_out null): CL_E_CAPACITY, *n_out holds the need and nothing was written.  A malformed stream (the cases of
+ * cl_edit_profile, and a read position past 2^32 - 1) is CL_E_INVALID, the text naming the first such read; *n_out = 0 and nothing is
+ * handed out; it never makes the kernel read or write out of range. */
+cl_status cl_overlaps_of(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read,
+                         const uint32_t* d_ref_read, uint32_t n_ref_read, uint32_t max_blocks, cl_overlap* d_out, uint64_t cap, uint64_t* n_out);
+/* The same on the HOST (references as in cl_edit_profile_host), a sequential walk with the same checks in the same order; h_out may be
+ * null to ask for the count.  bad_read / bad_code (optional): the first malformed read and its code (cl_edit_profile_error). */
+cl_status cl_overlaps_host(const uint8_t* h_ref_codes, const uint64_t* h_ref_off, uint32_t n_refs, const uint8_t* h_es, const uint64_t* h_es_off, uint64_t n_reads,
+                           uint64_t first_read, const uint32_t* h_ref_read, uint32_t n_ref_read, cl_overlap* h_out, uint64_t cap, uint64_t* n_out, uint64_t* bad_read, uint32_t* bad_code);
+/* Opt-in (off by default: one flag test per batch, no launch, no allocation, every output byte the same).  While it is on, every batch
+ * of tuple streams made on this context — by cl_compress_shard, by cl_compressor_encode, or by an encode lane of a compressor created on
+ * it — leaves its records on the host, `t` translated to input indices.  cl_ctx_overlaps: those of this context and its compressor's
+ * lanes so far, in input order (h_out, cap records; CL_E_CAPACITY with *n_out = the need and nothing written when cap is too small);
+ * switching the flag on drops what was kept.  A compressor that shares its reads with other ranks, and the pseudo reads of a reference
+ * genome, are refused while the flag is on (CL_E_UNSUPPORTED): their reference ids are not reads of this compressor's input. */
+void cl_ctx_set_overlaps(cl_ctx* ctx, int on);
+cl_status cl_ctx_overlaps(const cl_ctx* ctx, cl_overlap* h_out, uint64_t cap, uint64_t* n_out);
+
 /* ---- a14 + a16: CDNACoder / CEntrComprReads (dna_coder.{h,cpp}, entr_read.h:56-80) --------------------- */
 typedef struct cl_dna_coder cl_dna_coder;
 /* CDNACoder::Init(true, maxCandidates, level, ., n_ref_genome_pseudo_reads): one adaptive model set that
@@ -675,6 +716,8 @@ cl_status cl_compressor_edit_profile(const cl_compressor* c, cl_edits* out);
 /* cl_ctx_kmer_spectrum of the compressor's context (cl_ctx_set_kmer_spectrum): after cl_compressor_count_finish, the spectrum of the
  * k-mers pass 1 counted (a reference genome's included) */
 cl_status cl_compressor_kmer_spectrum(const cl_compressor* c, cl_kspec* out);
+/* cl_ctx_overlaps of the compressor's context (cl_ctx_set_overlaps): after the last cl_compressor_encode, of every chunk */
+cl_status cl_compressor_overlaps(const cl_compressor* c, cl_overlap* h_out, uint64_t cap, uint64_t* n_out);
 
 /* cl_qual_coder_set_domain_symbols / cl_qual_coder_domains of the compressor's quality coder.  The setting must be made before the
  * first cl_compressor_encode or cl_compressor_prepare_parts call (CL_E_INVALID afterwards, and without a quality stream); the `dna`
