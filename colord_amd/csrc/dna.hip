@@ -12,7 +12,7 @@
 #include "objects.hpp"
 #include "rc_dev.hpp"
 #include "rc_check.hpp"    // the opt-in check of the coded parts (cl_ctx_set_verify_streams)
-#include "es_format.hpp"      // tuple types and EsReader, shared with expand.hip
+#include "es_format.hpp"      // EsReader; the tuple types of es_codes.hpp
 #include <algorithm>
 #include <deque>
 #include <thread>

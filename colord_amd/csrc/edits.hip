@@ -1,9 +1,9 @@
 // edits.hip — the edit-operation profile of a batch on the device (edits.hpp): cl_edit_profile over the tuple streams that
 // cl_encode_reads wrote and the reference arena they point to; the host form's C entry; the pipeline's hook (edit_profile_chunk).
 //
-// k_edit_profile walks the streams as k_es_expand does (expand.hip): ONE WAVE PER READ, the stream 64 bytes per window
-// (a byte per lane), the tuple starts from three ballots, the window cut into stretches on one reference, a wave prefix sum of the
-// cursor advances inside a stretch, the alternative-id table in one VGPR pair.  It stores nothing and copies no anchor: an anchor
+// k_edit_profile walks the streams as es_wave.hpp describes: ONE WAVE PER READ, the stream 64 bytes per window (a byte per lane), the
+// tuple starts from three ballots, the window cut into stretches on one reference; here a wave prefix sum of the cursor advances
+// inside a stretch.  It stores nothing and copies no anchor: an anchor
 // counts by its length, which the prefix sum carries anyway.  So a read costs its stream bytes / 64 plus one ref_base() per del,
 // match or subst tuple.  Per window:
 //   - tuples by type: popcounts of `starts & ballot(type)`, kept in uniform registers until the read's end;
@@ -19,14 +19,12 @@
 // (`since`, the same in every thread); the block flushes before a quad that would take that past 2^32 - 1, and a quad that alone
 // holds more is not counted and makes the call CL_E_UNSUPPORTED.
 //
-// Bounds by construction, in the terms of expand.hip: a window never holds a byte at or past es_off[r + 1] and a tuple that would
-// cross it is an error; every reference id is checked against the arena's read count before its length is loaded; every reference
-// base comes through ref_base(), which answers 255 outside the read (an error, never an access); a cell index is below ED_WORDS
+// Bounds by construction: those of es_wave.hpp, and: a cell index is below ED_WORDS
 // where it is formed (base values are rejected above 3, subst values above 2, bit lengths and run lengths clamped) and ep_count
 // drops any that is not.  A malformed stream gives its read an error code; the call is CL_E_INVALID and adds nothing.
 #include "common.hpp"
 #include "objects.hpp"
-#include "es_format.hpp"
+#include "es_wave.hpp"
 #include "edits.hpp"
 #include <memory>
 #include <mutex>
@@ -40,16 +38,6 @@ __host__ __device__ inline uint32_t ep_sum_word(uint32_t k) { return k < 3 ? ED_
 constexpr uint32_t EP_ERR = EP_SLOTS * ED_WORDS, EP_BIG = EP_ERR + 1, EP_G_WORDS = EP_BIG + 1;
 constexpr uint64_t EP_CELL_MAX = 0xffffffffULL;
 
-struct Arena { const uint64_t* packed; const uint64_t* word_off; const uint32_t* lens; uint32_t n; };
-struct RefCursor { uint32_t id = 0, len = 0; uint64_t wo = 0; bool rev = false; };
-// GetRefRead(id, rev)[pos] with the guard 255 (reference_reads.h:142-207), as in expand.hip; `c` was made from an id below the arena's read count
-__device__ inline uint32_t ref_base(const Arena& R, const RefCursor& c, uint64_t pos)
-{
-	if (pos >= c.len) return 255;
-	const uint32_t p = c.rev ? c.len - 1 - (uint32_t)pos : (uint32_t)pos;
-	const uint32_t b = (uint32_t)(R.packed[c.wo + (p >> 5)] >> (62 - 2 * (p & 31))) & 3u;
-	return c.rev ? 3u - b : b;
-}
 __device__ inline uint32_t ep_bit_len(uint32_t v) { const uint32_t b = v ? 32u - (uint32_t)__clz((int)v) : 0u; return b > 28 ? 28u : b; }
 
 // every lane's cell (ED_WORDS and above: none) counted: one LDS atomic per lane that has one, nothing returned, so the wave goes on while
@@ -81,193 +69,132 @@ __device__ inline void ep_flush(uint32_t* s_cnt, unsigned long long* s_sum, unsi
 __device__ inline uint32_t ep_read(const Arena& R, const uint8_t* __restrict__ s, uint64_t n, uint32_t lane, uint32_t* s_cnt, unsigned long long* s_sum)
 {
 	uint32_t err = EDE_NONE, lane_err = EDE_NONE;                               // uniform; what a tuple of mine ran into
-	const uint32_t hb = lane < 5 && lane < n ? (uint32_t)s[lane] : 0u;          // the start tuple
-	const uint32_t b0 = __builtin_amdgcn_readfirstlane(hb), t0 = b0 >> 4;
+	const EsStart st = es_start(s, n, lane, R.n);
 	uint32_t kind = 2; uint64_t bases = 0;
 	uint32_t cnt[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, n_alt = 0, n_entries = 0;    // uniform, of this read
 	uint64_t anchor_sum = 0, skip_sum = 0, entry_sum = 0;
 	bool main_rev = false;
-	if (t0 == T_START_PLAIN || t0 == T_START_PLAIN_N)
+	if (st.plain)
 	{	// the rest of the stream is `plain` tuples: a lane per base
-		kind = t0 == T_START_PLAIN ? 0u : 1u;
-		for (uint64_t i = 1 + lane; i < n; i += 64)
-		{
-			const uint32_t b = s[i];
-			if ((b >> 4) != T_PLAIN) lane_err = EDE_TYPE; else if ((b & 0xf) > 4) lane_err = EDE_VALUE;
-		}
+		kind = st.t0 == T_START_PLAIN ? 0u : 1u;
+		lane_err = es_plain_check(s, n, lane);
 		bases = n - 1;
 	}
-	else if (t0 != T_START_ES) err = EDE_START;
-	else if (n < 5) err = EDE_TRUNC;
+	else if (st.err) err = st.err;
 	else
 	{
-		const uint32_t main_id = __builtin_amdgcn_readfirstlane((__shfl(hb, 1, 64) << 24) | (__shfl(hb, 2, 64) << 16) | (__shfl(hb, 3, 64) << 8) | __shfl(hb, 4, 64));
-		main_rev = (b0 & 0xf) != 0;
-		if (main_id >= R.n) err = EDE_REF_ID;
-		else
+		main_rev = st.rev;
+		EsRefs<true> F(R, st);
+		uint32_t last_type = T_START_ES, open_type = T_NONE, open_len = 0;      // across windows: the last tuple's type; the open run of ins / del
+		uint64_t pos = 5;
+		while (!err && pos < n)
 		{
-			RefCursor mainc; mainc.id = main_id; mainc.len = R.lens[main_id]; mainc.wo = R.word_off[main_id]; mainc.rev = main_rev;
-			RefCursor cur = mainc;
-			uint64_t cursor = 0, main_cursor = 0; bool is_main = true;
-			uint32_t my_alt_id = 0, my_alt_rev = 0;                                 // lane i: alternative i of this read and the orientation it came with first
-			uint32_t last_type = T_START_ES, open_type = T_NONE, open_len = 0;      // across windows: the last tuple's type; the open run of ins / del
-			uint64_t pos = 5;
-			while (!err && pos < n)
+			const EsWindow W = es_window(s, pos, n, lane);
+			if (W.err) { err = W.err; break; }
+			const uint32_t b = W.b, t = W.t, p = W.p, v28 = W.v28, adv = es_ref_adv(W);
+			const uint64_t starts = W.starts, m5 = W.m5; const bool is_start = W.is_start;
+			// the tuples of each type
+			const uint64_t mI = starts & __ballot(t == T_INS), mD = starts & __ballot(t == T_DEL), mM = starts & __ballot(t == T_MATCH), mS = starts & __ballot(t == T_SUBST);
+			const uint64_t anch = starts & __ballot(t == T_ANCHOR), mK = starts & __ballot(t == T_SKIP), mA = starts & m5, mR = starts & __ballot(t == T_MAIN_REF);
+			cnt[T_INS] += (uint32_t)__popcll(mI); cnt[T_DEL] += (uint32_t)__popcll(mD); cnt[T_MATCH] += (uint32_t)__popcll(mM); cnt[T_SUBST] += (uint32_t)__popcll(mS);
+			cnt[T_ANCHOR] += (uint32_t)__popcll(anch); cnt[T_SKIP] += (uint32_t)__popcll(mK); cnt[T_ALT_ID] += (uint32_t)__popcll(mA); cnt[T_MAIN_REF] += (uint32_t)__popcll(mR);
+			// skips whose preceding tuple is an alt-id (five bytes before them, or the last tuple of the window before): entry positions
+			const uint64_t ent = mK & ((mA << 5) | (last_type == T_ALT_ID ? 1ull : 0ull));
+			n_entries += (uint32_t)__popcll(ent);
+			// runs of ins / del: runs of set bits; the one that reaches the window's last tuple stays open while the stream goes on
+			uint32_t cell_run = ED_WORDS;
 			{
-				const uint32_t wn = n - pos < 64 ? (uint32_t)(n - pos) : 64u;       // bytes of this window: never one at or past the stream's end
-				const uint32_t b = lane < wn ? (uint32_t)s[pos + lane] : 0xffu;
-				const uint32_t t = b >> 4;
-				const uint64_t m1 = __ballot(lane < wn && (t <= T_SUBST || t == T_MAIN_REF));
-				const uint64_t m4 = __ballot(lane < wn && (t == T_ANCHOR || t == T_SKIP));
-				const uint64_t m5 = __ballot(lane < wn && t == T_ALT_ID);
-				uint64_t starts = 0; uint32_t p = 0;                                // p: bytes of the window that whole tuples take
-				while (p < wn)
-				{
-					const uint64_t bit = 1ull << p;
-					if (m1 & bit)
-					{	// the run of one-byte tuples from here
-						const uint64_t z = ~(m1 >> p);
-						const uint32_t k = z ? (uint32_t)__builtin_ctzll(z) : 64u;
-						starts |= (k >= 64 ? ~0ull : (1ull << k) - 1) << p; p += k;
-					}
-					else if (m4 & bit) { if (p + 4 > wn) break; starts |= bit; p += 4; }
-					else if (m5 & bit) { if (p + 5 > wn) break; starts |= bit; p += 5; }
-					else { err = EDE_TYPE; break; }
-				}
-				if (!err && p == 0) err = EDE_TRUNC;                                // (a window of 64 bytes holds any tuple: this one ends past the stream)
-				if (err) break;
-				const bool is_start = (starts >> lane) & 1;
-				const uint32_t b1 = __shfl_down(b, 1, 64), b2 = __shfl_down(b, 2, 64), b3 = __shfl_down(b, 3, 64), b4 = __shfl_down(b, 4, 64);   // (a start's payload is inside the window)
-				const uint32_t v28 = ((b & 0xf) << 24) | (b1 << 16) | (b2 << 8) | b3;
-				const uint32_t id32 = (b1 << 24) | (b2 << 16) | (b3 << 8) | b4;
-				const uint32_t adv = !is_start ? 0u : (t == T_DEL || t == T_MATCH || t == T_SUBST) ? 1u : (t == T_ANCHOR || t == T_SKIP) ? v28 : 0u;
-				// the tuples of each type
-				const uint64_t mI = starts & __ballot(t == T_INS), mD = starts & __ballot(t == T_DEL), mM = starts & __ballot(t == T_MATCH), mS = starts & __ballot(t == T_SUBST);
-				const uint64_t anch = starts & __ballot(t == T_ANCHOR), mK = starts & __ballot(t == T_SKIP), mA = starts & m5, mR = starts & __ballot(t == T_MAIN_REF);
-				cnt[T_INS] += (uint32_t)__popcll(mI); cnt[T_DEL] += (uint32_t)__popcll(mD); cnt[T_MATCH] += (uint32_t)__popcll(mM); cnt[T_SUBST] += (uint32_t)__popcll(mS);
-				cnt[T_ANCHOR] += (uint32_t)__popcll(anch); cnt[T_SKIP] += (uint32_t)__popcll(mK); cnt[T_ALT_ID] += (uint32_t)__popcll(mA); cnt[T_MAIN_REF] += (uint32_t)__popcll(mR);
-				// skips whose preceding tuple is an alt-id (five bytes before them, or the last tuple of the window before): entry positions
-				const uint64_t ent = mK & ((mA << 5) | (last_type == T_ALT_ID ? 1ull : 0ull));
-				n_entries += (uint32_t)__popcll(ent);
-				// runs of ins / del: runs of set bits; the one that reaches the window's last tuple stays open while the stream goes on
-				uint32_t cell_run = ED_WORDS;
-				{
-					const bool more = pos + p < n;
-					uint32_t new_type = T_NONE, new_len = 0;
+				const bool more = pos + p < n;
+				uint32_t new_type = T_NONE, new_len = 0;
 #pragma unroll
-					for (int k = 0; k < 2; ++k)
-					{
-						const uint64_t M = k ? mD : mI; const uint32_t ty = k ? T_DEL : T_INS, hist = k ? ED_DEL_RUN : ED_INS_RUN;
-						const uint32_t carry_len = open_type == ty ? open_len : 0u;
-						if (open_type == ty && !(M & 1) && lane == 0) atomicAdd(&s_cnt[hist + ed_run_bin(open_len)], 1u);      // the open run ends with this window's first tuple
-						const bool tail_open = more && ((M >> (p - 1)) & 1);
-						if ((M >> lane) & 1)
-						{
-							const bool is_end = lane == 63 || !((M >> (lane + 1)) & 1);
-							if (is_end && !(tail_open && lane == p - 1))
-							{
-								const uint64_t below = ~M & ((1ull << lane) - 1);       // the tuples before me that are not of my type
-								const uint32_t start = below ? 64u - (uint32_t)__builtin_clzll(below) : 0u;
-								cell_run = hist + ed_run_bin((uint64_t)(lane - start + 1) + (start == 0 ? carry_len : 0u));
-							}
-						}
-						if (tail_open)
-						{
-							const uint64_t z = ~(M << (64 - p));
-							const uint32_t tl = z ? (uint32_t)__builtin_clzll(z) : 64u;     // its tuples in this window (<= p)
-							new_type = ty; new_len = tl + (tl == p ? carry_len : 0u);
-						}
-					}
-					open_type = new_type; open_len = new_len;
-				}
-				// what a tuple adds to the sparse fields: one cell per lane
-				uint32_t cell = ED_WORDS;
-				if (is_start)
+				for (int k = 0; k < 2; ++k)
 				{
-					if (t == T_INS) { if ((b & 0xf) > 3) lane_err = EDE_VALUE; else cell = ED_INS_BASE + (b & 0xf); }
-					else if (t == T_ANCHOR) cell = ED_ANCHOR_LEN + ep_bit_len(v28);
-					else if (t == T_SKIP && !((ent >> lane) & 1)) cell = ED_SKIP_LEN + ep_bit_len(v28);
-				}
-				const uint64_t sw = mA | mR;                                        // tuples that change the reference
-				const uint64_t unit_adv = mD | mM | mS;
-				uint64_t todo = starts;
-				while (todo && !err)
-				{	// a stretch of tuples on one reference, then the tuple that ends it
-					const uint64_t swm = todo & sw;
-					const uint32_t sl = swm ? (uint32_t)__builtin_ctzll(swm) : 64u;
-					const uint64_t seg = sl >= 64 ? todo : todo & ((1ull << sl) - 1);
-					if (seg)
+					const uint64_t M = k ? mD : mI; const uint32_t ty = k ? T_DEL : T_INS, hist = k ? ED_DEL_RUN : ED_INS_RUN;
+					const uint32_t carry_len = open_type == ty ? open_len : 0u;
+					if (open_type == ty && !(M & 1) && lane == 0) atomicAdd(&s_cnt[hist + ed_run_bin(open_len)], 1u);      // the open run ends with this window's first tuple
+					const bool tail_open = more && ((M >> (p - 1)) & 1);
+					if ((M >> lane) & 1)
 					{
-						const bool in_seg = (seg >> lane) & 1;
-						const uint32_t ad = in_seg ? adv : 0u;                      // (at most 16 multi-byte tuples of 28 bits: the sums fit 32 bits)
-						const uint32_t ai = wave_incl_scan(ad);
-						const uint32_t atot = __builtin_amdgcn_readfirstlane(__shfl(ai, 63, 64));
-						if (in_seg && (t == T_DEL || t == T_MATCH || t == T_SUBST))
+						const bool is_end = lane == 63 || !((M >> (lane + 1)) & 1);
+						if (is_end && !(tail_open && lane == p - 1))
 						{
-							const uint32_t rb = ref_base(R, cur, cursor + (ai - ad)), v = b & 0xf;
-							if (rb > 3) lane_err = EDE_GUARD;
-							else if (t == T_DEL) cell = ED_DEL_BASE + rb;
-							else if (t == T_MATCH) cell = ED_MATCH_BASE + rb;
-							else if (v > 2) lane_err = EDE_VALUE;
-							else cell = ED_SUB + 4 * rb + v + (v >= rb ? 1u : 0u);      // v-th of the three bases other than the reference's
+							const uint64_t below = ~M & ((1ull << lane) - 1);       // the tuples before me that are not of my type
+							const uint32_t start = below ? 64u - (uint32_t)__builtin_clzll(below) : 0u;
+							cell_run = hist + ed_run_bin((uint64_t)(lane - start + 1) + (start == 0 ? carry_len : 0u));
 						}
-						uint64_t seg_anchor = 0;
-						for (uint64_t am = seg & anch; am; am &= am - 1)
-						{	// an anchor: its length, and that it lies on its reference
-							const uint32_t l = (uint32_t)__builtin_ctzll(am);
-							const uint32_t alen = __builtin_amdgcn_readfirstlane(__shfl(v28, l, 64));
-							const uint64_t a_c = cursor + (__builtin_amdgcn_readfirstlane(__shfl(ai, l, 64)) - alen);
-							if (a_c + alen > cur.len) { err = EDE_GUARD; break; }
-							seg_anchor += alen;
-						}
-						if (err) break;
-						// the stretch's skips: its advance but the unit tuples and the anchors; an entry position can only be its first tuple
-						uint64_t seg_skip = (uint64_t)atot - (uint64_t)__popcll(seg & unit_adv) - seg_anchor;
-						const uint32_t fl = (uint32_t)__builtin_ctzll(seg);
-						if ((ent >> fl) & 1) { const uint32_t e = __builtin_amdgcn_readfirstlane(__shfl(v28, fl, 64)); entry_sum += e; seg_skip -= e; }
-						anchor_sum += seg_anchor; skip_sum += seg_skip;
-						cursor += atot;
 					}
-					if (sl >= 64) break;
-					if (__shfl(t, sl, 64) == T_MAIN_REF)
-					{	// back to the main reference where it was left
-						if (!is_main) { cur = mainc; cursor = main_cursor; is_main = true; }
-					}
-					else
+					if (tail_open)
 					{
-						const uint32_t id = __builtin_amdgcn_readfirstlane(__shfl(id32, sl, 64));
-						const uint32_t orient = (__shfl(b, sl, 64) & 0xf) != 0 ? 1u : 0u;
-						if (id >= R.n) { err = EDE_REF_ID; break; }
-						if (is_main) { main_cursor = cursor; is_main = false; }
-						const uint64_t hit = __ballot(lane < n_alt && my_alt_id == id);
-						uint32_t rev;
-						if (hit) rev = __shfl(my_alt_rev, (uint32_t)__builtin_ctzll(hit), 64);      // the orientation of its first appearance holds
-						else
-						{
-							if (n_alt >= ED_MAX_ALT) { err = EDE_TOO_MANY_ALT; break; }
-							if (lane == n_alt) { my_alt_id = id; my_alt_rev = orient; }
-							++n_alt; rev = orient;
-						}
-						cur.id = id; cur.len = R.lens[id]; cur.wo = R.word_off[id]; cur.rev = rev != 0;
-						cursor = 0;
+						const uint64_t z = ~(M << (64 - p));
+						const uint32_t tl = z ? (uint32_t)__builtin_clzll(z) : 64u;     // its tuples in this window (<= p)
+						new_type = ty; new_len = tl + (tl == p ? carry_len : 0u);
 					}
-					todo &= ~(((1ull << sl) << 1) - 1);
 				}
-				if (err) break;
-				ep_count(s_cnt, cell);
-				ep_count(s_cnt, cell_run);
-				last_type = __builtin_amdgcn_readfirstlane(__shfl(t, 63u - (uint32_t)__builtin_clzll(starts), 64));
-				pos += p;
-				const uint64_t le = __ballot(lane_err != EDE_NONE);
-				if (le) err = __shfl(lane_err, (uint32_t)__builtin_ctzll(le), 64);
+				open_type = new_type; open_len = new_len;
 			}
-			bases = (uint64_t)cnt[T_INS] + cnt[T_MATCH] + cnt[T_SUBST] + anchor_sum;
+			// what a tuple adds to the sparse fields: one cell per lane
+			uint32_t cell = ED_WORDS;
+			if (is_start)
+			{
+				if (t == T_INS) { if ((b & 0xf) > 3) lane_err = EDE_VALUE; else cell = ED_INS_BASE + (b & 0xf); }
+				else if (t == T_ANCHOR) cell = ED_ANCHOR_LEN + ep_bit_len(v28);
+				else if (t == T_SKIP && !((ent >> lane) & 1)) cell = ED_SKIP_LEN + ep_bit_len(v28);
+			}
+			const uint64_t sw = mA | mR;                                        // tuples that change the reference
+			const uint64_t unit_adv = mD | mM | mS;
+			uint64_t todo = starts;
+			while (todo && !err)
+			{	// a stretch of tuples on one reference, then the tuple that ends it
+				const EsStretch x = es_stretch(todo, sw);
+				const uint64_t seg = x.seg;
+				if (seg)
+				{
+					const bool in_seg = (seg >> lane) & 1;
+					const uint32_t ad = in_seg ? adv : 0u;                      // (at most 16 multi-byte tuples of 28 bits: the sums fit 32 bits)
+					const uint32_t ai = wave_incl_scan(ad);
+					const uint32_t atot = __builtin_amdgcn_readfirstlane(__shfl(ai, 63, 64));
+					if (in_seg && (t == T_DEL || t == T_MATCH || t == T_SUBST))
+					{
+						const uint32_t rb = ref_base(R, F.cur, F.cursor + (ai - ad)), v = b & 0xf;
+						if (rb > 3) lane_err = EDE_GUARD;
+						else if (t == T_DEL) cell = ED_DEL_BASE + rb;
+						else if (t == T_MATCH) cell = ED_MATCH_BASE + rb;
+						else if (v > 2) lane_err = EDE_VALUE;
+						else cell = ED_SUB + 4 * rb + v + (v >= rb ? 1u : 0u);      // v-th of the three bases other than the reference's
+					}
+					uint64_t seg_anchor = 0;
+					for (uint64_t am = seg & anch; am; am &= am - 1)
+					{	// an anchor: its length, and that it lies on its reference
+						const uint32_t l = (uint32_t)__builtin_ctzll(am);
+						const uint32_t alen = __builtin_amdgcn_readfirstlane(__shfl(v28, l, 64));
+						const uint64_t a_c = F.cursor + (__builtin_amdgcn_readfirstlane(__shfl(ai, l, 64)) - alen);
+						if (a_c + alen > F.cur.len) { err = EDE_GUARD; break; }
+						seg_anchor += alen;
+					}
+					if (err) break;
+					// the stretch's skips: its advance but the unit tuples and the anchors; an entry position can only be its first tuple
+					uint64_t seg_skip = (uint64_t)atot - (uint64_t)__popcll(seg & unit_adv) - seg_anchor;
+					const uint32_t fl = (uint32_t)__builtin_ctzll(seg);
+					if ((ent >> fl) & 1) { const uint32_t e = __builtin_amdgcn_readfirstlane(__shfl(v28, fl, 64)); entry_sum += e; seg_skip -= e; }
+					anchor_sum += seg_anchor; skip_sum += seg_skip;
+					F.cursor += atot;
+				}
+				if (x.sl >= 64) break;
+				if (__shfl(t, x.sl, 64) == T_MAIN_REF) F.to_main();
+				else if ((err = F.to_alt(R, W, x.sl, lane))) break;
+				todo = es_behind(todo, x.sl);
+			}
+			if (err) break;
+			ep_count(s_cnt, cell);
+			ep_count(s_cnt, cell_run);
+			last_type = __builtin_amdgcn_readfirstlane(__shfl(t, 63u - (uint32_t)__builtin_clzll(starts), 64));
+			pos += p;
+			err = es_lane_err(lane_err);
 		}
+		n_alt = F.n_alt;
+		bases = (uint64_t)cnt[T_INS] + cnt[T_MATCH] + cnt[T_SUBST] + anchor_sum;
 	}
-	{
-		const uint64_t le = __ballot(lane_err != EDE_NONE);
-		if (!err && le) err = __shfl(lane_err, (uint32_t)__builtin_ctzll(le), 64);
-	}
+	if (!err) err = es_lane_err(lane_err);
 	err = __builtin_amdgcn_readfirstlane(err);
 	if (err) return err;
 	// the read's own counts: tuples by type from lanes 0..7, the rest from lane 0
@@ -354,7 +281,7 @@ extern "C" cl_status cl_edit_profile(cl_ctx* ctx, const cl_reads* refs, const ui
 	const uint32_t grid = std::min(grid_for(n_reads, 4), max_blocks);
 	DevBuf<unsigned long long> g; DEV_ALLOC(ctx, g, EP_G_WORDS);
 	HIP_TRY(ctx, hipMemsetAsync(g.p, 0, EP_G_WORDS * 8, cl_launch_stream(ctx)));
-	const Arena R{ refs->packed.p, refs->word_off.p, refs->lens.p, refs->n_reads };
+	const Arena R{ refs->packed.p, nullptr, refs->word_off.p, refs->lens.p, refs->n_reads };
 	LAUNCH(ctx, k_edit_profile, grid, 256, R, d_es, d_es_off, n_reads, flush_bytes, g.p);
 	HIP_TRY(ctx, hipGetLastError());
 	std::vector<unsigned long long> h(EP_G_WORDS);

@@ -1,11 +1,8 @@
-// es_format.hpp — the tuple-stream byte format (es_t, utils.h:56-273) as the device code reads it: the tuple types and the
-// sequential reader.  Shared by the DNA coder's walk (dna.hip) and by the expander that inverts a10-a12 (expand.hip).
-//   type in the high nibble of the first byte;  1 byte: ins, del, match, subst, main-ref, plain, start-plain, start-plain-with-Ns;
-//   4 bytes: anchor, skip (28-bit big-endian value);  5 bytes: alt-id, start-es (low nibble = orientation, 32-bit big-endian id)
+// es_format.hpp — the tuple stream (es_codes.hpp: the format and the tuple types) read sequentially on the device: the reader of the
+// DNA coder's walk (dna.hip).  The wave-level walk of the kernels that take a read per wave is es_wave.hpp.
 #pragma once
 #include "common.hpp"
-
-enum { T_INS = 0, T_DEL, T_MATCH, T_SUBST, T_ANCHOR, T_SKIP, T_ALT_ID, T_MAIN_REF, T_PLAIN, T_START_PLAIN, T_START_ES, T_START_PLAIN_N, T_NONE };
+#include "es_codes.hpp"
 
 struct EsReader {
 	const uint8_t* p; const uint8_t* e;

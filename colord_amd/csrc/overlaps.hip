@@ -1,48 +1,43 @@
 // overlaps.hip — read-to-read overlaps from the edit scripts on the device (overlaps.hpp): cl_overlaps_of over the tuple
 // streams that cl_encode_reads wrote; the host form's C entry; the pipeline's hook (overlaps_chunk) and what a context keeps.
 //
-// k_overlap_walk<FILL> walks the streams as k_edit_profile does (edits.hip): ONE WAVE PER READ, the stream 64 bytes per window (a byte
-// per lane), the tuple starts from three ballots, the window cut into stretches on one reference at alt-id / main-ref, a wave prefix sum
-// of the cursor advances inside a stretch, the alternative-id table in one VGPR pair.  It adds a second prefix sum, of the advances of
-// the READ position, and the open visit's state, which is uniform: a stretch's first and last aligned lane come from ctz / clz of
-// `stretch & (match | subst | anchor > 0)`, matches and subst from popcounts plus the anchor sum.  It loads no reference base: a
-// position is checked against the reference's length alone.  The tuple that ends a stretch closes the visit; so does the stream's end.
+// k_overlap_walk<FILL> walks the streams as es_wave.hpp describes: ONE WAVE PER READ, the stream 64 bytes per window (a byte per lane),
+// the tuple starts from three ballots, the window cut into stretches on one reference at alt-id / main-ref.  Here, inside a stretch, two
+// wave prefix sums — of the cursor advances and of the advances of the READ position — and the open visit's state, which is uniform: a
+// stretch's first and last aligned lane come from ctz / clz of `stretch & (match | subst | anchor > 0)`, matches and subst from popcounts
+// plus the anchor sum.  It loads no reference base: a position is checked against the reference's length alone (EsRefs<false>: a cursor
+// without its word offset).  The tuple that ends a stretch closes the visit; so does the stream's end.
 // ONE body, two instantiations, so that the count and the fill cannot disagree: FILL = false writes n_rec[r] and qlen[r]; a prefix sum
 // (cl_scan_u32_u64) gives the offsets; FILL = true has lane 0 store the k-th closed visit's record at off[r] + k.
 // Persistent blocks of four waves stride over the reads; no LDS, no barrier.
 //
-// The window and stretch code is a SECOND COPY of ep_read's, not shared with it: there the per-window counting (runs of ins / del, one
-// cell per lane, the entry skips) sits between the ballots and inside the stretch loop, and a shared form would have to take both
-// kernels' per-stretch work as callbacks with a dozen captured registers each — a rewrite of k_edit_profile (131 VGPRs today) for no
-// line saved there.  What the two must agree on — the checks and their codes — is pinned by the shared malformed streams of the suites.
-//
-// Bounds by construction, in the terms of edits.hip and expand.hip: every loop bound is known before the loop (a window is the
+// Bounds by construction, in the terms of es_wave.hpp: every loop bound is known before the loop (a window is the
 // min(64, bytes left) bytes in front of es_off[r + 1]; the tuple-start loop and the stretch loop run over at most 64 bits of a mask; the
 // read loop over n_reads); a window never holds a byte at or past es_off[r + 1] and a tuple that would cross it is an error; every
-// reference id is checked against the arena's read count — and against the translation table's size — before lens[] or the table is
-// indexed with it; no reference base is loaded at all.  Stores: n_rec[r] and qlen[r] for r < n_reads; a record only at off[r] + k while
+// reference id is checked against the arena's read count and the translation table's size (OvRefs::A.n is the smaller of the two) before
+// lens[] or the table is indexed with it; no reference base is loaded at all.  Stores: n_rec[r] and qlen[r] for r < n_reads; a record only at off[r] + k while
 // that is below off[r + 1], and the host has checked off[n_reads] <= cap before the fill is launched.  A malformed stream gives its read
 // an error code; the call is CL_E_INVALID and hands nothing out.
 #include "common.hpp"
 #include "objects.hpp"
-#include "es_format.hpp"
+#include "es_wave.hpp"
 #include "overlaps.hpp"
 #include <algorithm>
 #include <mutex>
 
 namespace {
-struct OvRefs { const uint32_t* lens; uint32_t n; const uint32_t* ref_read; uint32_t n_ref_read; };      // ref_read: null, or id -> input index (n_ref_read entries)
-struct OvCursor { uint32_t id = 0, len = 0; bool rev = false; };
+// A: lens and n alone, n = the ids that may be met; ref_read: null, or id -> input index (at least A.n entries)
+struct OvRefs { Arena A; const uint32_t* ref_read; };
 
 // the open visit closed: a record if it holds an aligned column.  Uniform; lane 0 stores (FILL), three 16-byte vector stores.
-template<bool FILL> __device__ inline void ov_close(OvVisit& V, uint32_t& n_rec, const OvRefs& R, const OvCursor& cur, bool is_main, uint32_t q, uint32_t qlen, uint32_t lane,
+template<bool FILL> __device__ inline void ov_close(OvVisit& V, uint32_t& n_rec, const OvRefs& R, const RefCursor& cur, bool is_main, uint32_t q, uint32_t qlen, uint32_t lane,
                                                     cl_overlap* __restrict__ out, uint64_t o0, uint64_t o1)
 {
 	if (V.has)
 	{
 		if (FILL && lane == 0 && o0 + n_rec < o1)
 		{
-			const cl_overlap o = ov_record(V, q, R.ref_read ? R.ref_read[cur.id] : cur.id, qlen, cur.len, cur.rev, is_main);      // (cur.id < n_ref_read: checked where the id was met)
+			const cl_overlap o = ov_record(V, q, R.ref_read ? R.ref_read[cur.id] : cur.id, qlen, cur.len, cur.rev, is_main);      // (cur.id < A.n: checked where the id was met)
 			uint4* dst = reinterpret_cast<uint4*>(out + o0 + n_rec);
 			dst[0] = make_uint4(o.q, o.t, o.qlen, o.tlen); dst[1] = make_uint4(o.qs, o.qe, o.ts, o.te); dst[2] = make_uint4(o.matches, o.subst, o.anchor_bases, o.flags);
 		}
@@ -56,155 +51,90 @@ template<bool FILL> __device__ inline uint32_t ov_read(const OvRefs& R, const ui
                                                        cl_overlap* __restrict__ out, uint64_t o0, uint64_t o1, uint32_t& n_rec, uint64_t& qpos_out)
 {
 	uint32_t err = EDE_NONE, lane_err = EDE_NONE;                               // uniform; what a tuple of mine ran into
-	const uint32_t hb = lane < 5 && lane < n ? (uint32_t)s[lane] : 0u;          // the start tuple
-	const uint32_t b0 = __builtin_amdgcn_readfirstlane(hb), t0 = b0 >> 4;
+	const EsStart st = es_start(s, n, lane, R.A.n);
 	uint64_t qpos = 0;
 	n_rec = 0;
-	if (t0 == T_START_PLAIN || t0 == T_START_PLAIN_N)
+	if (st.plain)
 	{	// the rest of the stream is `plain` tuples, a lane per base: no record, the same checks as the profile's
-		for (uint64_t i = 1 + lane; i < n; i += 64)
-		{
-			const uint32_t b = s[i];
-			if ((b >> 4) != T_PLAIN) lane_err = EDE_TYPE; else if ((b & 0xf) > 4) lane_err = EDE_VALUE;
-		}
+		lane_err = es_plain_check(s, n, lane);
 		qpos = n - 1;
 	}
-	else if (t0 != T_START_ES) err = EDE_START;
-	else if (n < 5) err = EDE_TRUNC;
+	else if (st.err) err = st.err;
 	else
 	{
-		const uint32_t main_id = __builtin_amdgcn_readfirstlane((__shfl(hb, 1, 64) << 24) | (__shfl(hb, 2, 64) << 16) | (__shfl(hb, 3, 64) << 8) | __shfl(hb, 4, 64));
-		if (main_id >= R.n || (R.ref_read && main_id >= R.n_ref_read)) err = EDE_REF_ID;
-		else
+		EsRefs<false> F(R.A, st);
+		OvVisit V;                                                             // the open visit (uniform)
+		uint64_t pos = 5;
+		while (!err && pos < n)
 		{
-			OvCursor mainc; mainc.id = main_id; mainc.len = R.lens[main_id]; mainc.rev = (b0 & 0xf) != 0;
-			OvCursor cur = mainc;
-			uint64_t cursor = 0, main_cursor = 0; bool is_main = true;
-			uint32_t my_alt_id = 0, my_alt_rev = 0, n_alt = 0;                     // lane i: alternative i of this read and the orientation it came with first
-			OvVisit V;                                                             // the open visit (uniform)
-			uint64_t pos = 5;
-			while (!err && pos < n)
+			const EsWindow W = es_window(s, pos, n, lane);
+			if (W.err) { err = W.err; break; }
+			const uint32_t b = W.b, t = W.t, v28 = W.v28; const uint64_t starts = W.starts; const bool is_start = W.is_start;
+			// what a tuple advances the reference cursor and the read position by
+			const uint32_t adv = es_ref_adv(W), qadv = es_read_adv(W);
+			const uint64_t mM = starts & __ballot(t == T_MATCH), mS = starts & __ballot(t == T_SUBST), anch = starts & __ballot(t == T_ANCHOR);
+			const uint64_t aligned = mM | mS | (starts & __ballot(t == T_ANCHOR && v28 > 0));
+			const uint64_t sw = starts & (W.m5 | __ballot(t == T_MAIN_REF));      // tuples that change the reference
+			if (is_start)
 			{
-				const uint32_t wn = n - pos < 64 ? (uint32_t)(n - pos) : 64u;       // bytes of this window: never one at or past the stream's end
-				const uint32_t b = lane < wn ? (uint32_t)s[pos + lane] : 0xffu;
-				const uint32_t t = b >> 4;
-				const uint64_t m1 = __ballot(lane < wn && (t <= T_SUBST || t == T_MAIN_REF));
-				const uint64_t m4 = __ballot(lane < wn && (t == T_ANCHOR || t == T_SKIP));
-				const uint64_t m5 = __ballot(lane < wn && t == T_ALT_ID);
-				uint64_t starts = 0; uint32_t p = 0;                                // p: bytes of the window that whole tuples take
-				while (p < wn)
-				{
-					const uint64_t bit = 1ull << p;
-					if (m1 & bit)
-					{	// the run of one-byte tuples from here
-						const uint64_t z = ~(m1 >> p);
-						const uint32_t k = z ? (uint32_t)__builtin_ctzll(z) : 64u;
-						starts |= (k >= 64 ? ~0ull : (1ull << k) - 1) << p; p += k;
-					}
-					else if (m4 & bit) { if (p + 4 > wn) break; starts |= bit; p += 4; }
-					else if (m5 & bit) { if (p + 5 > wn) break; starts |= bit; p += 5; }
-					else { err = EDE_TYPE; break; }
-				}
-				if (!err && p == 0) err = EDE_TRUNC;                                // (a window of 64 bytes holds any tuple: this one ends past the stream)
-				if (err) break;
-				const bool is_start = (starts >> lane) & 1;
-				const uint32_t b1 = __shfl_down(b, 1, 64), b2 = __shfl_down(b, 2, 64), b3 = __shfl_down(b, 3, 64), b4 = __shfl_down(b, 4, 64);   // (a start's payload is inside the window)
-				const uint32_t v28 = ((b & 0xf) << 24) | (b1 << 16) | (b2 << 8) | b3;
-				const uint32_t id32 = (b1 << 24) | (b2 << 16) | (b3 << 8) | b4;
-				// what a tuple advances the reference cursor and the read position by
-				const uint32_t adv = !is_start ? 0u : (t == T_DEL || t == T_MATCH || t == T_SUBST) ? 1u : (t == T_ANCHOR || t == T_SKIP) ? v28 : 0u;
-				const uint32_t qadv = !is_start ? 0u : (t == T_INS || t == T_MATCH || t == T_SUBST) ? 1u : t == T_ANCHOR ? v28 : 0u;
-				const uint64_t mM = starts & __ballot(t == T_MATCH), mS = starts & __ballot(t == T_SUBST), anch = starts & __ballot(t == T_ANCHOR);
-				const uint64_t aligned = mM | mS | (starts & __ballot(t == T_ANCHOR && v28 > 0));
-				const uint64_t sw = starts & (m5 | __ballot(t == T_MAIN_REF));      // tuples that change the reference
-				if (is_start)
-				{
-					if (t == T_INS && (b & 0xf) > 3) lane_err = EDE_VALUE;
-					if (t == T_SUBST && (b & 0xf) > 2) lane_err = EDE_VALUE;
-				}
-				uint64_t todo = starts;
-				while (todo && !err)
-				{	// a stretch of tuples on one reference, then the tuple that ends it
-					const uint64_t swm = todo & sw;
-					const uint32_t sl = swm ? (uint32_t)__builtin_ctzll(swm) : 64u;
-					const uint64_t seg = sl >= 64 ? todo : todo & ((1ull << sl) - 1);
-					if (seg)
-					{
-						const bool in_seg = (seg >> lane) & 1;
-						const uint32_t ad = in_seg ? adv : 0u, qd = in_seg ? qadv : 0u;    // (at most 16 multi-byte tuples of 28 bits: the sums fit 32 bits)
-						const uint32_t ai = wave_incl_scan(ad), qi = wave_incl_scan(qd);
-						const uint32_t atot = __builtin_amdgcn_readfirstlane(__shfl(ai, 63, 64)), qtot = __builtin_amdgcn_readfirstlane(__shfl(qi, 63, 64));
-						if (in_seg && (t == T_DEL || t == T_MATCH || t == T_SUBST) && cursor + (ai - ad) >= cur.len) lane_err = lane_err ? lane_err : (uint32_t)EDE_GUARD;
-						uint64_t seg_anchor = 0;
-						for (uint64_t am = seg & anch; am; am &= am - 1)
-						{	// an anchor: its length, and that it lies on its reference
-							const uint32_t l = (uint32_t)__builtin_ctzll(am);
-							const uint32_t alen = __builtin_amdgcn_readfirstlane(__shfl(v28, l, 64));
-							const uint64_t a_c = cursor + (__builtin_amdgcn_readfirstlane(__shfl(ai, l, 64)) - alen);
-							if (a_c + alen > cur.len) { err = EDE_GUARD; break; }
-							seg_anchor += alen;
-						}
-						if (err) break;
-						const uint64_t al = seg & aligned;
-						if (al)
-						{	// the visit's interval: from in front of its first aligned column to behind its last
-							const uint32_t fl = (uint32_t)__builtin_ctzll(al), ll = 63u - (uint32_t)__builtin_clzll(al);
-							if (!V.has)
-							{
-								V.has = true;
-								V.qs = qpos + __builtin_amdgcn_readfirstlane(__shfl(qi - qd, fl, 64));
-								V.ts_o = cursor + __builtin_amdgcn_readfirstlane(__shfl(ai - ad, fl, 64));
-							}
-							V.qe = qpos + __builtin_amdgcn_readfirstlane(__shfl(qi, ll, 64));
-							V.te_o = cursor + __builtin_amdgcn_readfirstlane(__shfl(ai, ll, 64));
-							V.matches += (uint64_t)__popcll(seg & mM) + seg_anchor; V.subst += (uint64_t)__popcll(seg & mS); V.anchor_bases += seg_anchor;
-						}
-						cursor += atot; qpos += qtot;
-					}
-					if (sl >= 64) break;
-					// the tuple that ends the stretch: a position error inside the visit comes first (the host form meets it first)
-					{
-						const uint64_t le = __ballot(lane_err != EDE_NONE && lane < sl);
-						if (le) { err = __builtin_amdgcn_readfirstlane(__shfl(lane_err, (uint32_t)__builtin_ctzll(le), 64)); break; }
-					}
-					if (__shfl(t, sl, 64) == T_MAIN_REF)
-					{	// closes the visit, and back to the main reference where it was left
-						ov_close<FILL>(V, n_rec, R, cur, is_main, q, qlen, lane, out, o0, o1);
-						if (!is_main) { cur = mainc; cursor = main_cursor; is_main = true; }
-					}
-					else
-					{
-						const uint32_t id = __builtin_amdgcn_readfirstlane(__shfl(id32, sl, 64));
-						const uint32_t orient = (__shfl(b, sl, 64) & 0xf) != 0 ? 1u : 0u;
-						if (id >= R.n || (R.ref_read && id >= R.n_ref_read)) { err = EDE_REF_ID; break; }
-						ov_close<FILL>(V, n_rec, R, cur, is_main, q, qlen, lane, out, o0, o1);
-						if (is_main) { main_cursor = cursor; is_main = false; }
-						const uint64_t hit = __ballot(lane < n_alt && my_alt_id == id);
-						uint32_t rev;
-						if (hit) rev = __shfl(my_alt_rev, (uint32_t)__builtin_ctzll(hit), 64);      // the orientation of its first appearance holds
-						else
-						{
-							if (n_alt >= ED_MAX_ALT) { err = EDE_TOO_MANY_ALT; break; }
-							if (lane == n_alt) { my_alt_id = id; my_alt_rev = orient; }
-							++n_alt; rev = orient;
-						}
-						cur.id = id; cur.len = R.lens[id]; cur.rev = __builtin_amdgcn_readfirstlane(rev) != 0;
-						cursor = 0;
-					}
-					todo &= ~(((1ull << sl) << 1) - 1);
-				}
-				if (err) break;
-				pos += p;
-				const uint64_t le = __ballot(lane_err != EDE_NONE);
-				if (le) err = __shfl(lane_err, (uint32_t)__builtin_ctzll(le), 64);
+				if (t == T_INS && (b & 0xf) > 3) lane_err = EDE_VALUE;
+				if (t == T_SUBST && (b & 0xf) > 2) lane_err = EDE_VALUE;
 			}
-			if (!err) ov_close<FILL>(V, n_rec, R, cur, is_main, q, qlen, lane, out, o0, o1);      // the stream's end closes the last visit
+			uint64_t todo = starts;
+			while (todo && !err)
+			{	// a stretch of tuples on one reference, then the tuple that ends it
+				const EsStretch x = es_stretch(todo, sw);
+				const uint64_t seg = x.seg; const uint32_t sl = x.sl;
+				if (seg)
+				{
+					const bool in_seg = (seg >> lane) & 1;
+					const uint32_t ad = in_seg ? adv : 0u, qd = in_seg ? qadv : 0u;    // (at most 16 multi-byte tuples of 28 bits: the sums fit 32 bits)
+					const uint32_t ai = wave_incl_scan(ad), qi = wave_incl_scan(qd);
+					const uint32_t atot = __builtin_amdgcn_readfirstlane(__shfl(ai, 63, 64)), qtot = __builtin_amdgcn_readfirstlane(__shfl(qi, 63, 64));
+					if (in_seg && (t == T_DEL || t == T_MATCH || t == T_SUBST) && F.cursor + (ai - ad) >= F.cur.len) lane_err = lane_err ? lane_err : (uint32_t)EDE_GUARD;
+					uint64_t seg_anchor = 0;
+					for (uint64_t am = seg & anch; am; am &= am - 1)
+					{	// an anchor: its length, and that it lies on its reference
+						const uint32_t l = (uint32_t)__builtin_ctzll(am);
+						const uint32_t alen = __builtin_amdgcn_readfirstlane(__shfl(v28, l, 64));
+						const uint64_t a_c = F.cursor + (__builtin_amdgcn_readfirstlane(__shfl(ai, l, 64)) - alen);
+						if (a_c + alen > F.cur.len) { err = EDE_GUARD; break; }
+						seg_anchor += alen;
+					}
+					if (err) break;
+					const uint64_t al = seg & aligned;
+					if (al)
+					{	// the visit's interval: from in front of its first aligned column to behind its last
+						const uint32_t fl = (uint32_t)__builtin_ctzll(al), ll = 63u - (uint32_t)__builtin_clzll(al);
+						if (!V.has)
+						{
+							V.has = true;
+							V.qs = qpos + __builtin_amdgcn_readfirstlane(__shfl(qi - qd, fl, 64));
+							V.ts_o = F.cursor + __builtin_amdgcn_readfirstlane(__shfl(ai - ad, fl, 64));
+						}
+						V.qe = qpos + __builtin_amdgcn_readfirstlane(__shfl(qi, ll, 64));
+						V.te_o = F.cursor + __builtin_amdgcn_readfirstlane(__shfl(ai, ll, 64));
+						V.matches += (uint64_t)__popcll(seg & mM) + seg_anchor; V.subst += (uint64_t)__popcll(seg & mS); V.anchor_bases += seg_anchor;
+					}
+					F.cursor += atot; qpos += qtot;
+				}
+				if (sl >= 64) break;
+				// the tuple that ends the stretch: a position error inside the visit comes first (the host form meets it first)
+				if ((err = es_lane_err(lane < sl ? lane_err : (uint32_t)EDE_NONE))) break;
+				// it closes the visit, which lies on the reference left (an alt-id out of range behind it: the read's error, nothing is handed out)
+				const bool to_main = __shfl(t, sl, 64) == T_MAIN_REF;
+				ov_close<FILL>(V, n_rec, R, F.cur, F.is_main, q, qlen, lane, out, o0, o1);
+				if (to_main) F.to_main();
+				else if ((err = F.to_alt(R.A, W, sl, lane))) break;
+				todo = es_behind(todo, sl);
+			}
+			if (err) break;
+			pos += W.p;
+			err = es_lane_err(lane_err);
 		}
+		if (!err) ov_close<FILL>(V, n_rec, R, F.cur, F.is_main, q, qlen, lane, out, o0, o1);      // the stream's end closes the last visit
 	}
-	{
-		const uint64_t le = __ballot(lane_err != EDE_NONE);
-		if (!err && le) err = __shfl(lane_err, (uint32_t)__builtin_ctzll(le), 64);
-	}
+	if (!err) err = es_lane_err(lane_err);
 	err = __builtin_amdgcn_readfirstlane(err);
 	if (!err && qpos > OV_POS_MAX) err = EDE_GUARD;                             // a read position that does not fit the record
 	qpos_out = qpos;
@@ -217,7 +147,7 @@ template<bool FILL> __global__ __launch_bounds__(256) void k_overlap_walk(OvRefs
                                                                           uint32_t* __restrict__ n_rec, uint32_t* __restrict__ qlen, const uint64_t* __restrict__ off,
                                                                           cl_overlap* __restrict__ out, unsigned long long* __restrict__ g_err)
 {
-	const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;      // (the wave's number is uniform: said so, the read's offsets are scalar loads)
 	for (uint64_t r64 = (uint64_t)blockIdx.x * 4 + w; r64 < n_reads; r64 += (uint64_t)gridDim.x * 4)      // (wave-uniform)
 	{
 		const uint32_t r = (uint32_t)r64;
@@ -257,7 +187,7 @@ static cl_status ov_run(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, 
 	DevBuf<uint32_t> n_rec, qlen; DevBuf<uint64_t> off; DevBuf<unsigned long long> g;
 	DEV_ALLOC(ctx, n_rec, n_reads); DEV_ALLOC(ctx, qlen, n_reads); DEV_ALLOC(ctx, off, (uint64_t)n_reads + 1); DEV_ALLOC(ctx, g, 1);
 	HIP_TRY(ctx, hipMemsetAsync(g.p, 0, 8, cl_launch_stream(ctx)));
-	const OvRefs R{ refs->lens.p, refs->n_reads, d_ref_read, d_ref_read ? n_ref_read : 0u };
+	const OvRefs R{ Arena{ nullptr, nullptr, nullptr, refs->lens.p, d_ref_read ? std::min(refs->n_reads, n_ref_read) : refs->n_reads }, d_ref_read };
 	LAUNCH(ctx, k_overlap_walk<false>, grid, 256, R, d_es, d_es_off, n_reads, (uint32_t)first_read, n_rec.p, qlen.p, (const uint64_t*)nullptr, (cl_overlap*)nullptr, g.p);
 	HIP_TRY(ctx, hipGetLastError());
 	unsigned long long h_err = 0;

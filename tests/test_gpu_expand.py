@@ -1,13 +1,16 @@
 """GPU suite for the inverse of the edit-script encoder (csrc/expand.hip): cl_es_expand rebuilds reads from their tuple streams and the
 reference reads, cl_es_verify compares the same walk with an arena.  Judges: the streams tapped from the unmodified reference (golden
 es.bin) against the goldens' own reads, the plain forms, and hand-made streams whose expected bases come from the pure-Python expander
-below, written from the format table of DESIGN.md section 4 (tuple type in the high nibble of the first byte; see expand_py)."""
+below, written from the format table of DESIGN.md section 4 (tuple type in the high nibble of the first byte; see expand_py); and the
+malformed streams of tests/editstreams.py that stay inside every buffer, which both entry points must refuse."""
 import numpy as np
 import pytest
 import torch
 from util import golden
 from test_gpu_dna import ref_subset, es_arrays
+from colord_amd import _native as N
 from colord_amd.fastq import ReadSet
+import editstreams as ES
 
 pytestmark = pytest.mark.gpu
 
@@ -207,3 +210,27 @@ def test_one_changed_insertion_is_one_bad_read(ctx, tapped):
     streams[i] = bytes(s)
     es, off, nt = to_device(streams, [e[1] for e in g.es], ctx.device)
     assert ctx.es_verify(reads, refs, es, off, nt) == (1, i)
+
+
+# ---- 5. malformed streams -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(ES.malformed_device()))
+def test_malformed_stream_is_refused(ctx, name):
+    """the malformed streams the profile and the overlaps take (they lie inside every buffer whether or not a check were missing), as read 0
+    next to a well-formed read 1: both entry points refuse the call and name the read and what it ran into; the well-formed one alone passes"""
+    bad, why = ES.malformed_device()[name]
+    ref_seqs = ES.references()
+    good = ES.b5(START_ES, 0, 1) + ES.b1(MATCH) * 3 + ES.b4(ANCHOR, 40) + ES.b5(ALT_ID, 1) + ES.b4(SKIP, 2) + ES.b4(ANCHOR, 33) + ES.b1(MAIN_REF) + ES.b1(SUBST, 1) + ES.b1(INS, 2)
+    bases, ntup = expand_py(good, ref_seqs)
+    refs = ctx.pack_readset(readset_of(ref_seqs))
+    both = ctx.pack_readset(readset_of([np.zeros(4, np.uint8), np.asarray(bases, np.uint8)]))
+    es, off, _ = to_device([bad, good], [0, ntup], ctx.device)
+    for call in (lambda: ctx.es_expand(refs, es, off), lambda: ctx.es_verify(both, refs, es, off)):
+        with pytest.raises(N.ColordHipError) as x:
+            call()
+        assert x.value.status == N.CL_E_INVALID and "read 0: " + why in str(x.value), str(x.value)
+    alone = ctx.pack_readset(readset_of([np.asarray(bases, np.uint8)]))
+    es, off, nt = to_device([good], [ntup], ctx.device)
+    codes, boff = ctx.es_expand(refs, es, off, nt)
+    assert boff.cpu().numpy().tolist() == [0, len(bases)] and codes.cpu().numpy().tolist() == bases
+    assert ctx.es_verify(alone, refs, es, off, nt) == (0, None)
+    refs.free(); both.free(); alone.free()
