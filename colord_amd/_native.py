@@ -77,6 +77,66 @@ class KSpec(C.Structure):
     as_dict = Report.as_dict
 
 
+class SketchEntry(C.Structure):
+    """cl_sketch_entry: one k-mer of a MinHash sketch, its cl_sketch_hash and its count."""
+    _fields_ = [("hash", C.c_uint64), ("count", C.c_uint64)]
+
+
+class Sketch:
+    """cl_sketch: the host-side accumulator of a k-mer MinHash sketch (no device needed).  entries are strictly ascending by hash; merging is
+    union by hash, counts of equal hashes add, the lowest `size` stay, `qualifying` adds."""
+
+    def __init__(self, size: int, min_count: int):
+        self.lib, self.h = load(), _P()
+        st = self.lib.cl_sketch_create(size, min_count, C.byref(self.h))
+        if st != CL_OK:
+            raise ColordHipError(st, "cl_sketch_create failed")
+
+    def close(self):
+        if self.h:
+            self.lib.cl_sketch_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self) -> dict:
+        size, mc, q, n = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        st = self.lib.cl_sketch_info(self.h, C.byref(size), C.byref(mc), C.byref(q), C.byref(n))
+        if st != CL_OK:
+            raise ColordHipError(st, "cl_sketch_info failed")
+        return {"size": size.value, "min_count": mc.value, "qualifying": q.value, "n": n.value}
+
+    def entries(self):
+        """(hashes, counts) as numpy uint64 arrays"""
+        import numpy as np
+        n = self.info()["n"]
+        buf = np.zeros((n, 2), np.uint64)
+        st = self.lib.cl_sketch_entries(self.h, buf.ctypes.data if n else None, n)
+        if st != CL_OK:
+            raise ColordHipError(st, "cl_sketch_entries failed")
+        return buf[:, 0].copy(), buf[:, 1].copy()
+
+    def as_dict(self) -> dict:
+        d = self.info()
+        d["hash"], d["count"] = self.entries()
+        return d
+
+    def merge(self, hashes, counts, qualifying: int):
+        """cl_sketch_merge: CL_E_INVALID (hashes not strictly ascending, a count of 0, parameters out of range) raises and merges nothing"""
+        import numpy as np
+        h, c = np.asarray(hashes, np.uint64), np.asarray(counts, np.uint64)
+        assert h.shape == c.shape and h.ndim == 1
+        buf = np.ascontiguousarray(np.stack([h, c], axis=1))
+        st = self.lib.cl_sketch_merge(self.h, buf.ctypes.data if len(h) else None, len(h), qualifying)
+        if st != CL_OK:
+            raise ColordHipError(st, "cl_sketch_merge refused the entries")
+        return self
+
+
 class Overlap(C.Structure):
     """cl_overlap: one visit of a read's edit script on one reference read that holds an aligned column; twelve little-endian uint32."""
     _fields_ = [(k, C.c_uint32) for k in ("q", "t", "qlen", "tlen", "qs", "qe", "ts", "te", "matches", "subst", "anchor_bases", "flags")]
@@ -154,6 +214,16 @@ _SIG = {
     "cl_ctx_set_kmer_spectrum": (None, [_P, C.c_int]),
     "cl_ctx_kmer_spectrum": (C.c_int32, [_P, C.POINTER(KSpec)]),
     "cl_compressor_kmer_spectrum": (C.c_int32, [_P, C.POINTER(KSpec)]),
+    "cl_sketch_hash": (C.c_uint64, [C.c_uint64]),
+    "cl_sketch_create": (C.c_int32, [C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "cl_sketch_free": (None, [_P]),
+    "cl_sketch_info": (C.c_int32, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cl_sketch_entries": (C.c_int32, [_P, _P, C.c_uint64]),
+    "cl_sketch_merge": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint64]),
+    "cl_kmer_sketch_runs": (C.c_int32, [_P, _P, _P, C.c_uint64, C.c_uint64, C.c_uint32, _P]),
+    "cl_ctx_set_kmer_sketch": (C.c_int32, [_P, C.c_int, C.c_uint32, C.c_uint32]),
+    "cl_ctx_kmer_sketch": (C.c_int32, [_P, _P]),
+    "cl_compressor_kmer_sketch": (C.c_int32, [_P, _P]),
     "cl_overlaps_of": (C.c_int32, [_P, _P, _P, _P, C.c_uint32, C.c_uint64, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cl_overlaps_host": (C.c_int32, [_P, _P, C.c_uint32, _P, _P, C.c_uint64, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint32)]),

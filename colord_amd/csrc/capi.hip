@@ -1,6 +1,7 @@
 // capi.hip — context management, host-side acceptor (a6) and thin exported wrappers.
 #include "common.hpp"
 #include "objects.hpp"
+#include "sketch.hpp"
 #include <cmath>
 #include <random>
 
@@ -121,6 +122,7 @@ extern "C" void cl_ctx_destroy(cl_ctx* c)
 	delete c->report_acc;
 	delete c->edits_acc;
 	delete c->kspec_acc;
+	delete c->sketch_acc;
 	const int dev = c->device;
 	delete c;
 	cl_device_pool_release(dev);

@@ -205,6 +205,7 @@ int run_compress(int argc, char** argv)
 	if (O.report) cl_ctx_set_report(ctx, 1);
 	if (O.edit_profile) cl_ctx_set_edit_profile(ctx, 1);
 	if (O.kmer_spectrum) cl_ctx_set_kmer_spectrum(ctx, 1);
+	if (O.sketch) ck(ctx, cl_ctx_set_kmer_sketch(ctx, 1, (uint32_t)O.sketch_size, (uint32_t)O.sketch_min_count), "cl_ctx_set_kmer_sketch");
 	if (O.overlaps) cl_ctx_set_overlaps(ctx, 1);
 	std::vector<uint64_t> report_lens;                         // --report: every read length, as the reader hands the reads over in pass 1 (N50 / N90)
 	ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, nullptr, estimated_bases(R), &cmp), "cl_compressor_create");
@@ -351,6 +352,14 @@ int run_compress(int argc, char** argv)
 		KSpecSet K;
 		ck(ctx, cl_compressor_kmer_spectrum(cmp, K.s.get()), "cl_compressor_kmer_spectrum");
 		add_kspec(ar, K, prm.cp, GM.on, 1, ks.tot_kmers, ks.n_unique);
+	}
+	if (O.sketch)
+	{
+		cl_sketch* sk = nullptr;
+		ck(ctx, cl_sketch_create((uint32_t)O.sketch_size, (uint32_t)O.sketch_min_count, &sk), "cl_sketch_create");
+		ck(ctx, cl_compressor_kmer_sketch(cmp, sk), "cl_compressor_kmer_sketch");
+		add_sketch(ar, sk, prm.cp, GM.on, 1);
+		cl_sketch_free(sk);
 	}
 	if (O.overlaps)
 	{

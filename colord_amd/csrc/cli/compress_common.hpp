@@ -11,6 +11,7 @@
 #include "edits_stream.hpp"
 #include "overlaps_stream.hpp"
 #include "kspec_stream.hpp"
+#include "sketch_stream.hpp"
 #include <ctime>
 #include <mutex>
 
@@ -348,6 +349,18 @@ inline void add_overlaps(ArchiveWriter& ar, const OverlapSet& S, uint64_t n_read
 	for (const cl_overlap& o : S.recs) if (o.q >= n_reads || o.t >= n_reads) die("internal: an overlap record names a read outside the input");
 	const std::vector<uint8_t> b = S.pack();
 	ar.add(ar.reg("hipoverlaps"), b.data(), b.size(), 0);
+}
+// --sketch: the `hipsketch` stream (sketch_stream.hpp), before finish_archive: the sketch the compressors' contexts made of the k-mers of pass 1, `sets`
+// independent sets merged
+inline void add_sketch(ArchiveWriter& ar, const cl_sketch* sk, const cl_compress_params& cp, bool genome, uint32_t sets)
+{
+	SketchSet S; uint64_t n = 0;
+	if (cl_sketch_info(sk, &S.size, &S.min_count, &S.qualifying, &n) != CL_OK) die("internal: no k-mer sketch");
+	S.e.resize(n);
+	if (cl_sketch_entries(sk, S.e.data(), n) != CL_OK) die("internal: no k-mer sketch");
+	S.flags = genome ? 1u : 0u; S.k = cp.k; S.f = cp.f; S.sets = sets;
+	const std::vector<uint8_t> b = S.pack();
+	ar.add(ar.reg("hipsketch"), b.data(), b.size(), 0);
 }
 // --report with a *-fix mode: the -D values must be qualities the report can index
 inline void check_report_options(const Options& O, bool with_qual)

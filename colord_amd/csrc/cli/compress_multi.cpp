@@ -21,6 +21,7 @@ struct RankOut {
 	uint64_t dna_base = 0, qual_base = 0, qual_framed = 0;     // where its framed `dna` / `qual` parts start in the file; bytes of the latter
 	uint64_t moved = 0;
 	std::unique_ptr<cl_kspec> kspec;                           // --kmer-spectrum: what this rank's context counted of the key range it owns (of its own k-mers: an independent domain)
+	uint64_t sketch_qualifying = 0; std::vector<cl_sketch_entry> sketch;   // --sketch: the sketch this rank's context made of the key range it owns (of its own k-mers: an independent domain)
 	std::unique_ptr<cl_edits> edits;                           // --edit-profile: what this rank's compressor and its lanes counted of their tuple streams
 	std::unique_ptr<cl_report> report;                         // --report: what this rank's compressor counted of its reads
 	cl_digest dig[3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } }, dig_all[3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } };      // --digest: dna / qual / (--digest-values) qual-values of this rank's reads; of all ranks (as gathered with the byte counts)
@@ -122,6 +123,7 @@ int run_compress_multi(const Options& O)
 		if (digest_values && !independent) cl_ctx_set_digest_values(ctx, 1);
 		if (O.edit_profile) cl_ctx_set_edit_profile(ctx, 1);
 		if (O.kmer_spectrum) cl_ctx_set_kmer_spectrum(ctx, 1);
+		if (O.sketch) ck(ctx, cl_ctx_set_kmer_sketch(ctx, 1, (uint32_t)O.sketch_size, (uint32_t)O.sketch_min_count), "cl_ctx_set_kmer_sketch");
 		if (O.report) cl_ctx_set_report(ctx, 1);                            // (the report has no read indices: a rank's and an independent domain's compressor count alike)
 		ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, T ? &X : nullptr, my_bases, &cmp), "cl_compressor_create");
 		if (GM.on) GM.count_kmers(ctx, cmp);
@@ -167,6 +169,16 @@ int run_compress_multi(const Options& O)
 		if (!O.stream_input) host.release();
 		ck(ctx, cl_compressor_count_finish(cmp, &RO.ks), "k-mer counting (exchange 1)");
 		if (O.kmer_spectrum) { RO.kspec.reset(new cl_kspec); ck(ctx, cl_compressor_kmer_spectrum(cmp, RO.kspec.get()), "cl_compressor_kmer_spectrum"); }
+		if (O.sketch)
+		{
+			cl_sketch* sk = nullptr; uint64_t ns = 0;
+			ck(ctx, cl_sketch_create((uint32_t)O.sketch_size, (uint32_t)O.sketch_min_count, &sk), "cl_sketch_create");
+			ck(ctx, cl_compressor_kmer_sketch(cmp, sk), "cl_compressor_kmer_sketch");
+			ck(ctx, cl_sketch_info(sk, nullptr, nullptr, &RO.sketch_qualifying, &ns), "cl_sketch_info");
+			RO.sketch.resize(ns);
+			ck(ctx, cl_sketch_entries(sk, RO.sketch.data(), ns), "cl_sketch_entries");
+			cl_sketch_free(sk);
+		}
 		if (GM.on) GM.add_pseudo_reads(ctx, cmp, ka.k);
 		for (size_t ci = 0; ci < chunks.size(); ++ci)
 		{
@@ -316,6 +328,14 @@ int run_compress_multi(const Options& O)
 		KSpecSet K; uint64_t tot_kmers = out[0].ks.tot_kmers, n_unique = out[0].ks.n_unique;
 		for (uint32_t r = 0; r < world; ++r) { if (out[r].kspec) ks_add(K.s.get(), out[r].kspec.get()); if (independent && r) { tot_kmers += out[r].ks.tot_kmers; n_unique += out[r].ks.n_unique; } }
 		add_kspec(ar, K, prm.cp, GM.on, independent ? world : 1, tot_kmers, n_unique);
+	}
+	if (O.sketch)
+	{	// the merge rule (sketch.hpp): exact over the ranks' disjoint key ranges of ONE k-mer set, and over independent domains, a set each
+		cl_sketch* sk = nullptr;
+		ck(nullptr, cl_sketch_create((uint32_t)O.sketch_size, (uint32_t)O.sketch_min_count, &sk), "cl_sketch_create");
+		for (uint32_t r = 0; r < world; ++r) ck(nullptr, cl_sketch_merge(sk, out[r].sketch.data(), out[r].sketch.size(), out[r].sketch_qualifying), "cl_sketch_merge");
+		add_sketch(ar, sk, prm.cp, GM.on, independent ? world : 1);
+		cl_sketch_free(sk);
 	}
 	finish_archive(ar, O, R, tot);
 	if (use_rccl) rccl.destroy_all();

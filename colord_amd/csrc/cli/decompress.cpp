@@ -7,6 +7,7 @@
 #include "edits_stream.hpp"
 #include "overlaps_stream.hpp"
 #include "kspec_stream.hpp"
+#include "sketch_stream.hpp"
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <ctime>
@@ -110,7 +111,7 @@ struct DeviceQualDecoder {
 
 int run_info(int argc, char** argv)
 {
-	bool want_report = false, want_edits = false, want_kspec = false, want_overlaps = false, names = false, json = false; std::vector<std::string> pos;
+	bool want_report = false, want_edits = false, want_kspec = false, want_sketch = false, want_overlaps = false, names = false, json = false; std::vector<std::string> pos;
 	uint64_t min_block = 0; bool has_min_block = false;
 	for (int i = 2; i < argc; ++i)
 	{
@@ -124,12 +125,12 @@ int run_info(int argc, char** argv)
 			min_block = strtoull(argv[++i], &end, 10); has_min_block = true;
 			if (*end) die("option --min-block needs a number");
 		}
-		else if (a == "--report") want_report = true; else if (a == "--edit-profile") want_edits = true; else if (a == "--kmer-spectrum") want_kspec = true; else if (a == "--json") json = true; else pos.push_back(a);
+		else if (a == "--report") want_report = true; else if (a == "--edit-profile") want_edits = true; else if (a == "--kmer-spectrum") want_kspec = true; else if (a == "--sketch") want_sketch = true; else if (a == "--json") json = true; else pos.push_back(a);
 	}
-	const int wanted = (want_report ? 1 : 0) + (want_edits ? 1 : 0) + (want_kspec ? 1 : 0);
+	const int wanted = (want_report ? 1 : 0) + (want_edits ? 1 : 0) + (want_kspec ? 1 : 0) + (want_sketch ? 1 : 0);
 	if (pos.size() != 1 || (json && !wanted) || wanted + (want_overlaps ? 1 : 0) > 1 || ((names || has_min_block) && !want_overlaps))
 	{
-		fprintf(stderr, "usage: colord_hip info [--report [--json]] [--edit-profile [--json]] [--kmer-spectrum [--json]] archive.colord\n       colord_hip info --overlaps [--min-block N] [--names] archive.colord\n");
+		fprintf(stderr, "usage: colord_hip info [--report [--json]] [--edit-profile [--json]] [--kmer-spectrum [--json]] archive.colord\n       colord_hip info --overlaps [--min-block N] [--names] archive.colord\n       colord_hip info --sketch [--json] archive.colord\n");
 		return 1;
 	}
 	const std::string& path = pos[0];
@@ -184,6 +185,15 @@ int run_info(int argc, char** argv)
 		if (json) print_kspec_json(stdout, K); else print_kspec(stdout, K);
 		return 0;
 	}
+	if (want_sketch)
+	{	// the stored k-mer sketch alone, on stdout: nothing is decoded
+		ar.close();
+		SketchSet K; const int have = read_hipsketch(path, K);
+		if (have == 0) die("no k-mer sketch is stored in this archive (written without --sketch)");
+		if (have < 0) die("the archive's `hipsketch` stream is not one this build reads");
+		if (json) print_sketch_json(stdout, K); else print_sketch(stdout, K);
+		return 0;
+	}
 	std::vector<uint8_t> b; uint64_t meta = 0;
 	if (!ar.part(ar.id("info"), 0, b, meta) || b.size() < 40) die("archive without a readable `info` stream");
 	ArchiveInfo I;
@@ -209,10 +219,50 @@ int run_info(int argc, char** argv)
 		fprintf(stderr, "k-mer spectrum: %llu sampled k-mers (1 in %u), %llu distinct, highest count %llu (`colord_hip info --kmer-spectrum [--json]` prints it)\n", (unsigned long long)ksp.s->kmers, ksp.f, (unsigned long long)ksp.s->distinct,
 			(unsigned long long)ksp.s->max_count);
 	else if (have < 0) fprintf(stderr, "k-mer spectrum: a `hipkmers` stream this build cannot read\n");
+	SketchSet skt;
+	if (const int have = read_hipsketch(path, skt); have > 0)
+		fprintf(stderr, "k-mer sketch: %llu of %llu qualifying k-mers (count >= %u, 1 in %u, k = %u), %s (`colord_hip info --sketch [--json]` prints it, `colord_hip dist` compares archives)\n", (unsigned long long)skt.e.size(),
+			(unsigned long long)skt.qualifying, skt.min_count, skt.f, skt.k, skt.complete() ? "complete" : "the lowest hashes");
+	else if (have < 0) fprintf(stderr, "k-mer sketch: a `hipsketch` stream this build cannot read\n");
 	OverlapSet ovl;
 	if (const int have = read_hipoverlaps(path, ovl); have > 0)
 		fprintf(stderr, "overlaps: %llu records of reads against reference reads (`colord_hip info --overlaps [--min-block N] [--names]` prints them as PAF)\n", (unsigned long long)ovl.recs.size());
 	else if (have < 0) fprintf(stderr, "overlaps: a `hipoverlaps` stream this build cannot read\n");
+	return 0;
+}
+
+// `colord_hip dist [--json] A.colord B.colord [C.colord ...]`: A against each of the others by their `hipsketch` streams alone (sketch_stream.hpp); no GPU
+int run_dist(int argc, char** argv)
+{
+	bool json = false; std::vector<std::string> pos;
+	for (int i = 2; i < argc; ++i) { const std::string a = argv[i]; if (a == "--json") json = true; else if (a.size() > 1 && a[0] == '-') { pos.clear(); break; } else pos.push_back(a); }
+	if (pos.size() < 2) { fprintf(stderr, "usage: colord_hip dist [--json] A.colord B.colord [C.colord ...]\n"); return 1; }
+	std::vector<SketchSet> S(pos.size());
+	for (size_t i = 0; i < pos.size(); ++i)
+	{
+		{ ArchiveReader ar; if (!ar.open(pos[i])) die("cannot open archive: " + pos[i]); ar.close(); }
+		const int have = read_hipsketch(pos[i], S[i]);
+		if (have == 0) die("no k-mer sketch is stored in " + pos[i] + " (written without --sketch)");
+		if (have < 0) die("the `hipsketch` stream of " + pos[i] + " is not one this build reads");
+		if (S[i].k != S[0].k || S[i].f != S[0].f)
+			die("sketches compare at equal k and f only: " + pos[i] + " has k = " + std::to_string(S[i].k) + ", f = " + std::to_string(S[i].f) + ", " + pos[0] + " has k = " + std::to_string(S[0].k) + ", f = " + std::to_string(S[0].f));
+	}
+	for (size_t i = 0; i < pos.size(); ++i)
+	{
+		if (i && S[i].min_count != S[0].min_count) fprintf(stderr, "colord_hip: note: %s was sketched with min_count %u, %s with %u: the k-mer sets were cut differently\n", pos[i].c_str(), S[i].min_count, pos[0].c_str(), S[0].min_count);
+		if (S[i].sets > 1) fprintf(stderr, "colord_hip: note: %s: %s\n", pos[i].c_str(), SKETCH_SETS_NOTE);
+		if (S[i].flags & 1) fprintf(stderr, "colord_hip: note: %s: the k-mers of a reference genome are in the sketch\n", pos[i].c_str());
+	}
+	// one line per pair: A, B, distance, jaccard, shared, compared, containment_of_A, containment_of_B
+	for (size_t i = 1; i < pos.size(); ++i)
+	{
+		const SketchDist D = sketch_dist(S[0], S[i]);
+		if (json)
+			printf("{\"a\": \"%s\", \"b\": \"%s\", \"k\": %u, \"f\": %u, \"shared\": %llu, \"compared\": %llu, \"in_a\": %llu, \"in_b\": %llu, \"jaccard\": %.17g, \"containment_of_a\": %.17g, \"containment_of_b\": %.17g, \"distance\": %.17g}\n",
+				json_escape(pos[0]).c_str(), json_escape(pos[i]).c_str(), S[0].k, S[0].f, (unsigned long long)D.shared, (unsigned long long)D.compared, (unsigned long long)D.in_a, (unsigned long long)D.in_b, D.jaccard, D.containment_a, D.containment_b, D.distance);
+		else
+			printf("%s\t%s\t%.17g\t%.17g\t%llu\t%llu\t%.17g\t%.17g\n", pos[0].c_str(), pos[i].c_str(), D.distance, D.jaccard, (unsigned long long)D.shared, (unsigned long long)D.compared, D.containment_a, D.containment_b);
+	}
 	return 0;
 }
 

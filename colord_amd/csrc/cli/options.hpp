@@ -42,6 +42,7 @@ struct Options {
 	bool report = false;                            // --report: the content report of the input (cl_ctx_set_report) in a `hipreport` stream
 	bool edit_profile = false;                      // --edit-profile: the edit-operation profile of the tuple streams (cl_ctx_set_edit_profile) in a `hipedits` stream
 	bool kmer_spectrum = false;                     // --kmer-spectrum: the count spectrum of the k-mers pass 1 counted (cl_ctx_set_kmer_spectrum) in a `hipkmers` stream
+	bool sketch = false; long sketch_size = -1, sketch_min_count = -1;   // --sketch [--sketch-size N] [--sketch-min-count M]: the MinHash sketch of the k-mers pass 1 counted at least M times (cl_ctx_set_kmer_sketch) in a `hipsketch` stream; defaults 10 000 and 2
 	bool overlaps = false;                          // --overlaps: the read-to-read overlaps the edit scripts hold (cl_ctx_set_overlaps) in a `hipoverlaps` stream
 	uint64_t qual_domain_symbols = 0;               // --qual-domain-symbols N: the quality models start afresh about every N symbols (cl_compressor_set_qual_domain_symbols; stream `hipqdomains`)
 	int gpus = 1; std::vector<int> gpu_list; std::string transport = "rccl";   // --gpus N [--gpu-list a,b,..] [--transport rccl|host]: reads sharded over N GPUs (run_compress_multi)
@@ -53,7 +54,7 @@ inline void usage()
 {
 	fprintf(stderr,
 		"usage: colord_hip compress-ont|compress-pbhifi|compress-pbraw [options] input.fastq|fasta[.gz] output.colord\n"
-		"       colord_hip decompress [--ignore-digest] [--gpu N] archive.colord output.fastq\n       colord_hip check [--gpu N] archive.colord\n       colord_hip info [--report [--json]] [--edit-profile [--json]] [--kmer-spectrum [--json]] archive.colord\n       colord_hip info --overlaps [--min-block N] [--names] archive.colord\n"
+		"       colord_hip decompress [--ignore-digest] [--gpu N] archive.colord output.fastq\n       colord_hip check [--gpu N] archive.colord\n       colord_hip info [--report [--json]] [--edit-profile [--json]] [--kmer-spectrum [--json]] archive.colord\n       colord_hip info --overlaps [--min-block N] [--names] archive.colord\n       colord_hip info --sketch [--json] archive.colord\n       colord_hip dist [--json] A.colord B.colord [C.colord ...]\n"
 		"options (as the reference, arg_parse.cpp:455-640):\n"
 		"  -p,--priority ratio|balanced|memory   -k,--kmer-len K with -a,--anchor-len A (both or none)\n"
 		"  -q,--qual org|none|avg|2-fix|4-fix|5-fix|2-avg|4-avg|5-avg   -T,--qual-thresholds a,b,..   -D,--qual-values a,b,..\n"
@@ -109,6 +110,18 @@ inline void usage()
 		"                     no estimate).  `decompress` / `check` do not recompute it.  Cost: one pass over 4 bytes per distinct sampled k-mer;\n"
 		"                     measured on an MI355X, 400 Mbases of synthetic ONT reads (33.3 M sampled k-mers, 27.6 M distinct): k_run_spectrum 0.077 ms of kernel time next to 2.61 ms of all kernels of\n"
 		"                     the same count, 0.10 ms of wall time on 2.90 ms; at 5 Gbases in the benchmark about 1 ms in a pass of 1.9 s, inside the run-to-run spread (DESIGN.md 9)\n"
+		"  --sketch [--sketch-size N] [--sketch-min-count M]   a bottom-N MinHash sketch of the sampled k-mers that occur at least M times (defaults 10 000 and 2; N up to 1 048 576) is made\n"
+		"                     on the device from the sorted keys of pass 1 and stored in the archive (stream `hipsketch`, 48 + 16 bytes per entry, 160 KB by default; the reference's\n"
+		"                     decompressor ignores it): the N smallest values of a 64-bit hash of the k-mers, each with the k-mer's count.  `colord_hip info --sketch [--json]` prints it,\n"
+		"                     `colord_hip dist [--json] A.colord B.colord [C.colord ...]` compares A with each of the others — Jaccard index, containment both ways and the distance\n"
+		"                     -ln(2j / (1 + j)) / k — from the sketches alone (tab-separated: A, B, distance, jaccard, shared, compared, containment of A, of B): no GPU, nothing decoded.  THE K-MERS ARE THE 1-IN-f HASH SAMPLE (-f) of reads with errors, cut at M (ONT\n"
+		"                     singletons are nearly all errors): sketches compare ONLY AT EQUAL k AND f, and the distance is not comparable with Mash distances of assembled genomes.\n"
+		"                     Works with --stream-input, --gpus N (the ranks own disjoint key ranges of one set: sets = 1, the same bytes), --domains K (K sets merged: M applies per set,\n"
+		"                     `qualifying` is a sum over the sets) and -G [-s] (the genome's k-mers are counted too: flag bit 0).  `decompress` / `check` ignore the stream.\n"
+		"                     Cost: two passes over 4 bytes per distinct sampled k-mer, 8 bytes per k-mer that occurs M times, and a sort of a few thousand pairs;\n"
+		"                     measured on an MI355X, 400 Mbases of synthetic ONT reads (27.6 M distinct sampled k-mers, 2.1 M of them counted twice or more): k_sketch_bins 0.146 ms, k_sketch_take\n"
+		"                     0.149 ms and 0.21 ms of sort kernels next to 2.68 ms of all kernels of the same count, 0.81 ms of wall time on 3.01 ms; from file to archive inside the spread of\n"
+		"                     three runs (DESIGN.md 4l, 9)\n"
 		"  --overlaps         the read-to-read overlaps that the edit scripts hold are stored in the archive (stream `hipoverlaps`, 48 bytes per record; the reference's decompressor ignores it):\n"
 		"                     one record per stretch of a read's edit script on ONE reference read that holds an aligned column — where on the read, where on the reference read in its\n"
 		"                     forward coordinates, strand, matches, substitutions, anchor bases — made on the device right behind the edit scripts.  `colord_hip info --overlaps\n"
@@ -187,6 +200,9 @@ inline Options parse_options(int argc, char** argv)
 		else if (a == "--report") O.report = true;
 		else if (a == "--edit-profile") O.edit_profile = true;
 		else if (a == "--kmer-spectrum") O.kmer_spectrum = true;
+		else if (a == "--sketch") O.sketch = true;
+		else if (a == "--sketch-size") { O.sketch_size = atol(need(i).c_str()); if (O.sketch_size < 1 || O.sketch_size > (1l << 20)) die("--sketch-size must be in [1, 1048576]"); }
+		else if (a == "--sketch-min-count") { O.sketch_min_count = atol(need(i).c_str()); if (O.sketch_min_count < 1 || O.sketch_min_count > 0x7fffffffl) die("--sketch-min-count must be in [1, 2147483647]"); }
 		else if (a == "--overlaps") O.overlaps = true;
 		else if (a == "--parse-threads") { O.parse_threads = atoi(need(i).c_str()); if (O.parse_threads < 1 || O.parse_threads > 256) die("--parse-threads must be in [1, 256]"); }
 		else if (a == "-h" || a == "--help") { usage(); exit(0); }
@@ -221,6 +237,8 @@ inline Options parse_options(int argc, char** argv)
 		if (O.domains > 1) die("--qual-domain-symbols is not available with --domains > 1");
 		if (P.qual_mode == 8) die("--qual-domain-symbols needs a coded quality stream: not with -q none (the default of compress-pbraw)");
 	}
+	if (!O.sketch && (O.sketch_size >= 0 || O.sketch_min_count >= 0)) { usage(); die("--sketch-size and --sketch-min-count need --sketch"); }
+	if (O.sketch) { if (O.sketch_size < 0) O.sketch_size = 10000; if (O.sketch_min_count < 0) O.sketch_min_count = 2; }
 	if (O.overlaps)
 	{	// a record names reads of the input: every reference id must be one of them, in ONE set of reference reads
 		if (O.gpus > 1) die("--overlaps is not available with --gpus > 1 (the ranks' reference ids are not translated to reads of the input yet)");

@@ -357,6 +357,8 @@ struct cl_ctx {
 	mutable std::mutex edits_mu;
 	bool kmer_spectrum = false;                  // cl_ctx_set_kmer_spectrum: count_range (kmer.hip) adds the count spectrum of every key range it counts (kspec.hip)
 	cl_kspec* kspec_acc = nullptr;               // the total so far (owner thread only); freed with the context
+	bool kmer_sketch = false;                    // cl_ctx_set_kmer_sketch: count_range (kmer.hip) merges the MinHash sketch of every key range it counts (sketch.hip)
+	cl_sketch* sketch_acc = nullptr;             // the sketch so far, with its parameters (sketch.hpp; owner thread only); freed with the context
 	bool overlaps = false;                       // cl_ctx_set_overlaps: tuple_streams (pass_steps.hpp) keeps the overlap records of every batch it makes (overlaps.hip)
 	std::map<uint64_t, std::vector<cl_overlap>> overlap_recs;   // the records of the batches made on THIS context by the batch's first read (under overlaps_mu: cl_ctx_overlaps merges the encode lanes')
 	mutable std::mutex overlaps_mu;

@@ -573,6 +573,7 @@ static cl_status count_range(cl_ctx* ctx, uint64_t* d_kmers, uint64_t n, uint32_
 		HIP_TRY(ctx, hipGetLastError());
 		flags.release();
 		if (ctx->kmer_spectrum) CL_TRY(kmer_spectrum_range(ctx, head_pos.p, n_heads, n));   // the whole count spectrum, before the cut at ci and the saturation at cs
+		if (ctx->kmer_sketch) CL_TRY(kmer_sketch_range(ctx, d_kmers, head_pos.p, n_heads, n));   // the MinHash sketch of the k-mers that occur often enough (sketch.hip)
 		DevBuf<uint32_t> kflags; DEV_ALLOC(ctx, kflags, n_heads);
 		LAUNCH(ctx, k_count_flags, grid_for(n_heads, 256), 256, (const uint32_t*)head_pos.p, n_heads, n, ci, kflags.p);
 		HIP_TRY(ctx, hipGetLastError());

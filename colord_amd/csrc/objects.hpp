@@ -68,6 +68,8 @@ cl_status report_chunk(cl_ctx* ctx, const cl_reads* reads, const cl_qual_params*
 cl_status edit_profile_chunk(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads);
 // kspec.hip (cl_ctx_set_kmer_spectrum): the count spectrum of one counted key range — the run starts of its n sorted keys — added to the context's total
 cl_status kmer_spectrum_range(cl_ctx* ctx, const uint32_t* d_head_pos, uint64_t n_heads, uint64_t n);
+// sketch.hip (cl_ctx_set_kmer_sketch): the MinHash sketch of one counted key range — its n sorted keys and the starts of their runs — merged into the context's
+cl_status kmer_sketch_range(cl_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_head_pos, uint64_t n_heads, uint64_t n);
 // overlaps.hip (cl_ctx_set_overlaps): the overlap records of a batch of tuple streams whose first read is read `first_read` of the input, kept on the
 // host by the context that made them; d_ref_read (n_ref_read entries, or null): reference id -> input index
 cl_status overlaps_chunk(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, const uint32_t* d_ref_read, uint32_t n_ref_read);

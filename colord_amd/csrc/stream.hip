@@ -463,6 +463,10 @@ extern "C" cl_status cl_compressor_kmer_spectrum(const cl_compressor* c, cl_kspe
 {
 	return c ? cl_ctx_kmer_spectrum(c->ctx, out) : CL_E_INVALID;
 }
+extern "C" cl_status cl_compressor_kmer_sketch(const cl_compressor* c, cl_sketch* out)
+{
+	return c ? cl_ctx_kmer_sketch(c->ctx, out) : CL_E_INVALID;
+}
 extern "C" cl_status cl_compressor_verified_streams(const cl_compressor* c, uint64_t* parts, uint64_t* symbols, uint64_t* bytes)
 {
 	if (!c) return CL_E_INVALID;

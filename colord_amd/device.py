@@ -58,6 +58,7 @@ class _OrderedLib:
                   "cl_report_clear", "cl_report_add", "cl_report_bases_host", "cl_report_quals_host", "cl_report_values_host", "cl_ctx_set_report", "cl_ctx_report", "cl_compressor_report",
                   "cl_edits_clear", "cl_edits_add", "cl_edit_profile_host", "cl_edit_profile_error", "cl_ctx_set_edit_profile", "cl_ctx_edit_profile", "cl_compressor_edit_profile",
                   "cl_kspec_clear", "cl_kspec_add", "cl_ctx_set_kmer_spectrum", "cl_ctx_kmer_spectrum", "cl_compressor_kmer_spectrum",
+                  "cl_sketch_hash", "cl_sketch_create", "cl_sketch_info", "cl_sketch_entries", "cl_sketch_merge", "cl_ctx_set_kmer_sketch", "cl_ctx_kmer_sketch", "cl_compressor_kmer_sketch",
                   "cl_overlaps_host", "cl_ctx_set_overlaps", "cl_ctx_overlaps", "cl_compressor_overlaps")
 
     def __init__(self, lib, device):
@@ -270,6 +271,27 @@ class Context:
             acc = N.KSpec()
             self.lib.cl_kspec_clear(C.byref(acc))
         _check(self, self.lib.cl_kmer_spectrum_heads(self.h, head_pos.data_ptr() if head_pos.numel() else None, head_pos.numel(), n, max_blocks, C.byref(acc)))
+        return acc
+
+    def set_kmer_sketch(self, on: bool = True, size: int = 10000, min_count: int = 2):
+        """cl_ctx_set_kmer_sketch: every count_filter() on this context, and the pass 1 of its compressors, merges the MinHash sketch of the
+        k-mers it counted at least min_count times (emptied, and its parameters set, when switched on)."""
+        _check(self, self.lib.cl_ctx_set_kmer_sketch(self.h, int(bool(on)), size, min_count))
+
+    def kmer_sketch(self) -> dict:
+        """cl_ctx_kmer_sketch: the sketch so far on this context: size, min_count, qualifying, n and the entries as numpy uint64 arrays."""
+        s = N.Sketch(0, 0)
+        _check(None, self.lib.cl_ctx_kmer_sketch(self.h, s.h))
+        return s.as_dict()
+
+    def kmer_sketch_runs(self, keys: torch.Tensor, head_pos: torch.Tensor, n: int, acc: "N.Sketch", max_blocks: int = 0) -> "N.Sketch":
+        """cl_kmer_sketch_runs: the sketch of the runs that start at the ascending positions head_pos (uint32 values, in a 4-byte dtype) of the
+        sorted array keys (64-bit) of n keys, merged into acc with acc's size and min_count.  A refusal raises (CL_E_INVALID) and leaves acc
+        as it is."""
+        assert head_pos.element_size() == 4 and keys.element_size() == 8
+        keys, head_pos = keys.contiguous(), head_pos.contiguous()
+        _check(self, self.lib.cl_kmer_sketch_runs(self.h, keys.data_ptr() if keys.numel() else None, head_pos.data_ptr() if head_pos.numel() else None,
+                                                  head_pos.numel(), n, max_blocks, acc.h))
         return acc
 
     @staticmethod

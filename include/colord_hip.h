@@ -510,6 +510,52 @@ cl_status cl_kmer_spectrum_heads(cl_ctx* ctx, const uint32_t* d_head_pos, uint64
 void cl_ctx_set_kmer_spectrum(cl_ctx* ctx, int on);
 cl_status cl_ctx_kmer_spectrum(const cl_ctx* ctx, cl_kspec* out);
 
+/* ---- k-mer MinHash sketch (no counterpart in the reference) — is this archive the same sample as that one? ------------- */
+/* Of the distinct sampled k-mers that occur at least min_count times (the runs of the sorted keys of cl_kmer_count_filter with that
+ * many keys), the `size` smallest values of cl_sketch_hash(kmer), each with the k-mer's count: a bottom-s MinHash sketch.
+ *   cl_sketch_hash(x) = fmix64(x ^ 0x9E3779B97F4A7C15), fmix64 being the finaliser of MurmurHash3 that the sampling test of
+ *   cl_kmer_scan uses on x itself (fmix64(x) % f == 0); the xor decouples the two.  fmix64 is a bijection of the 64-bit words: two
+ *   different k-mers never share a hash, and a k-mer can be recovered from its entry.  The same function runs on the device.
+ * The k-mers are the 1-in-f hash sample of cl_kmer_scan: sketches made with the same k and f have sampled the same sub-universe of
+ * k-mers and compare; sketches of another k or f do not.  WHAT IT IS NOT: a sketch of an assembly — it is made of noisy reads, so a
+ * distance from it is not comparable with Mash distances of genomes.
+ * cl_sketch is a host-side accumulator: size (1 .. 2^20), min_count (>= 1), qualifying — the distinct k-mers with count >=
+ * min_count, added over calls —, and n <= size entries strictly ascending by hash.  n < size means the sketch is COMPLETE: it holds
+ * every qualifying k-mer.  MERGE RULE, used by every path: union by hash, the counts of equal hashes add, the lowest `size` stay;
+ * qualifying adds.  That is exact over disjoint key ranges and ranks, where no hash can repeat.  It is exact for independent k-mer
+ * sets too (a hash in the union's bottom-`size` is in the bottom-`size` of every set that holds it, so its summed count is
+ * complete); min_count then applies PER SET and qualifying is a sum over the sets, which counts a k-mer once per set that holds it. */
+#define CL_SKETCH_MAX_SIZE (1u << 20)
+typedef struct cl_sketch_entry { uint64_t hash, count; } cl_sketch_entry;
+typedef struct cl_sketch cl_sketch;
+uint64_t cl_sketch_hash(uint64_t kmer);
+/* An empty accumulator with these parameters (any values: the calls that fill it refuse size 0, size > 2^20 and min_count 0). */
+cl_status cl_sketch_create(uint32_t size, uint32_t min_count, cl_sketch** out);
+void cl_sketch_free(cl_sketch* s);
+/* what it holds (any pointer may be NULL); its entries, ascending, into h_out (cap < n: CL_E_CAPACITY, nothing written) */
+cl_status cl_sketch_info(const cl_sketch* s, uint32_t* size, uint32_t* min_count, uint64_t* qualifying, uint64_t* n);
+cl_status cl_sketch_entries(const cl_sketch* s, cl_sketch_entry* h_out, uint64_t cap);
+/* The merge rule on the host: the n entries e (strictly ascending hashes, no count 0 — anything else is CL_E_INVALID and NOTHING is
+ * merged) and `qualifying` into *dst. */
+cl_status cl_sketch_merge(cl_sketch* dst, const cl_sketch_entry* e, uint64_t n, uint64_t qualifying);
+/* The sketch of the runs of a sorted key array of n keys (n < 2^32), merged into *acc (host) with acc's size and min_count:
+ * d_head_pos[0 .. n_heads) holds the ascending start positions of the runs (as cl_kmer_spectrum_heads), the key of run j is
+ * d_keys[d_head_pos[j]].  On the device: k_sketch_bins counts the qualifying hashes in 4096 bins by their top 12 bits (LDS, then
+ * 64-bit totals); the host takes the smallest bin B whose cumulative count reaches size; k_sketch_take writes the (hash, count)
+ * pairs of the bins <= B — a block takes 4096 runs and ONE place in the output —, a radix sort orders them, and the first
+ * min(size, candidates) come back.  max_blocks bounds both grids (0: the default, four per CU) and changes no result.
+ * CL_E_INVALID, and NOTHING is merged: positions that are not strictly ascending or not below n (they never make a kernel read or
+ * count out of range: a key is loaded at a validated position only), n_heads > n, n >= 2^32, acc's size 0 or above 2^20, acc's
+ * min_count 0.  n_heads == 0 is CL_OK and merges nothing. */
+cl_status cl_kmer_sketch_runs(cl_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_head_pos, uint64_t n_heads, uint64_t n, uint32_t max_blocks, cl_sketch* acc);
+/* Opt-in (off by default: one flag test per counted key range, no launch, no allocation, every output the same).  While it is on,
+ * every cl_kmer_count_filter on this context — the one-sort path and every key range above the count limit; in a multi-GPU run a
+ * rank's own key range — merges the sketch of what it counted.  Switching it on empties the context's sketch and sets its
+ * parameters (size 0 or above 2^20, or min_count 0: CL_E_INVALID, the switch stays as it was).  cl_ctx_kmer_sketch: *out becomes a
+ * copy of the context's sketch so far, parameters included (empty with size 0 if it was never switched on). */
+cl_status cl_ctx_set_kmer_sketch(cl_ctx* ctx, int on, uint32_t size, uint32_t min_count);
+cl_status cl_ctx_kmer_sketch(const cl_ctx* ctx, cl_sketch* out);
+
 /* ---- read-to-read overlaps (no counterpart in the reference) — what the edit scripts aligned, per read ---------------- */
 /* One record per VISIT of a read's tuple stream that holds an aligned column.  A visit is a stretch of tuples on one reference read:
  * it opens behind the start-es tuple and behind every alt-id / main-ref tuple; every alt-id and main-ref tuple closes the open one (a
@@ -716,6 +762,9 @@ cl_status cl_compressor_edit_profile(const cl_compressor* c, cl_edits* out);
 /* cl_ctx_kmer_spectrum of the compressor's context (cl_ctx_set_kmer_spectrum): after cl_compressor_count_finish, the spectrum of the
  * k-mers pass 1 counted (a reference genome's included) */
 cl_status cl_compressor_kmer_spectrum(const cl_compressor* c, cl_kspec* out);
+/* cl_ctx_kmer_sketch of the compressor's context (cl_ctx_set_kmer_sketch): after cl_compressor_count_finish, the sketch of the k-mers
+ * pass 1 counted (a reference genome's included); in a multi-GPU run of the key range this rank owns */
+cl_status cl_compressor_kmer_sketch(const cl_compressor* c, cl_sketch* out);
 /* cl_ctx_overlaps of the compressor's context (cl_ctx_set_overlaps): after the last cl_compressor_encode, of every chunk */
 cl_status cl_compressor_overlaps(const cl_compressor* c, cl_overlap* h_out, uint64_t cap, uint64_t* n_out);
 
