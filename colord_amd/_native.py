@@ -230,6 +230,12 @@ _SIG = {
     "cl_ctx_set_overlaps": (None, [_P, C.c_int]),
     "cl_ctx_overlaps": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cl_compressor_overlaps": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cl_mappings_lift": (C.c_int32, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cl_mappings_lift_host": (C.c_int32, [_P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "cl_ctx_set_mappings": (None, [_P, C.c_int]),
+    "cl_ctx_mappings": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cl_compressor_mappings": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cl_compressor_genome_geometry": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "cl_digest_bases": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(Digest)]),
     "cl_digest_quals": (C.c_int32, [_P, C.POINTER(QualParams), _P, _P, _P, C.c_uint64, C.POINTER(Digest)]),
     "cl_digest_bases_host": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(Digest)]),

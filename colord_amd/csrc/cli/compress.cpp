@@ -207,6 +207,7 @@ int run_compress(int argc, char** argv)
 	if (O.kmer_spectrum) cl_ctx_set_kmer_spectrum(ctx, 1);
 	if (O.sketch) ck(ctx, cl_ctx_set_kmer_sketch(ctx, 1, (uint32_t)O.sketch_size, (uint32_t)O.sketch_min_count), "cl_ctx_set_kmer_sketch");
 	if (O.overlaps) cl_ctx_set_overlaps(ctx, 1);
+	if (O.mappings) cl_ctx_set_mappings(ctx, 1);
 	std::vector<uint64_t> report_lens;                         // --report: every read length, as the reader hands the reads over in pass 1 (N50 / N90)
 	ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, nullptr, estimated_bases(R), &cmp), "cl_compressor_create");
 	if (O.qual_domain_symbols)
@@ -252,6 +253,11 @@ int run_compress(int argc, char** argv)
 	{
 		GM.add_pseudo_reads(ctx, cmp, k);
 		if (O.verbose) fprintf(stderr, "# ref genome pseudo reads: %u (length %u, overlap %u)\n", GM.n_pseudo, GM.read_len, GM.overlap);
+		if (O.mappings)
+		{	// the geometry the pieces were cut by: the library makes them again from it and refuses what does not give exactly the pseudo reads
+			const std::vector<uint64_t> sl = GM.seq_lens();
+			ck(ctx, cl_compressor_genome_geometry(cmp, sl.data(), (uint32_t)sl.size(), GM.read_len, GM.overlap), "cl_compressor_genome_geometry");
+		}
 	}
 	if (!O.stream_input) for (auto& dc : chunks) ck(ctx, cl_compressor_refs_add(cmp, dc.reads), "reference reads");
 	else
@@ -370,6 +376,16 @@ int run_compress(int argc, char** argv)
 		if (nv) ck(ctx, cl_compressor_overlaps(cmp, V.recs.data(), nv, &nv), "cl_compressor_overlaps");
 		add_overlaps(ar, V, n);
 		if (O.verbose) fprintf(stderr, "# overlaps: %llu records\n", (unsigned long long)nv);
+	}
+	if (O.mappings)
+	{
+		MappingSet V; uint64_t nv = 0;
+		const cl_status s = cl_compressor_mappings(cmp, nullptr, 0, &nv);
+		if (s != CL_OK && s != CL_E_CAPACITY) ck(ctx, s, "cl_compressor_mappings");
+		V.recs.resize(nv);
+		if (nv) ck(ctx, cl_compressor_mappings(cmp, V.recs.data(), nv, &nv), "cl_compressor_mappings");
+		add_mappings(ar, V, GM, O.genome, n);
+		if (O.verbose) fprintf(stderr, "# mappings: %llu records on %zu sequences\n", (unsigned long long)nv, V.seq_len.size());
 	}
 	if (O.qual_domain_symbols)
 	{

@@ -10,6 +10,7 @@
 #include "report_stream.hpp"
 #include "edits_stream.hpp"
 #include "overlaps_stream.hpp"
+#include "mappings_stream.hpp"
 #include "kspec_stream.hpp"
 #include "sketch_stream.hpp"
 #include <ctime>
@@ -121,6 +122,7 @@ struct GenomeMode {
 		if (st != CL_OK) die("cannot code the reference genome");
 		ar.add(stream, gs.data(), got, ns);
 	}
+	std::vector<uint64_t> seq_lens() const { std::vector<uint64_t> v; for (size_t s = 0; s + 1 < G.off.size(); ++s) v.push_back(G.off[s + 1] - G.off[s]); return v; }      // the kept bases of every sequence
 	void md5(uint8_t md[16]) const { if (cl_genome_md5(G.codes.data(), G.off.data(), (uint32_t)(G.off.size() - 1), md) != CL_OK) die("cannot checksum the reference genome"); }
 };
 
@@ -361,6 +363,17 @@ inline void add_sketch(ArchiveWriter& ar, const cl_sketch* sk, const cl_compress
 	S.flags = genome ? 1u : 0u; S.k = cp.k; S.f = cp.f; S.sets = sets;
 	const std::vector<uint8_t> b = S.pack();
 	ar.add(ar.reg("hipsketch"), b.data(), b.size(), 0);
+}
+// --mappings: the `hipmappings` stream (mappings_stream.hpp), before finish_archive: the geometry, the genome's sequence names and lengths, and the
+// records the compressor's context and its lanes kept, in input order; every record must name a read of the input and lie on its sequence
+inline void add_mappings(ArchiveWriter& ar, MappingSet& S, const GenomeMode& GM, const std::string& genome_path, uint64_t n_reads)
+{
+	S.read_len = GM.read_len; S.overlap = GM.overlap; S.seq_len = GM.seq_lens();
+	try { S.names = genome_io::read_fasta_names(genome_path); } catch (const std::exception& e) { die(e.what()); }
+	if (S.names.size() != S.seq_len.size()) die("internal: the reference genome has " + std::to_string(S.seq_len.size()) + " sequences and " + std::to_string(S.names.size()) + " names");
+	for (const cl_overlap& o : S.recs) if (o.q >= n_reads || o.t >= S.seq_len.size() || o.te > S.seq_len[o.t] || !(o.flags & OV_GENOME)) die("internal: a mapping record names a read outside the input or lies outside its sequence");
+	const std::vector<uint8_t> b = S.pack();
+	ar.add(ar.reg("hipmappings"), b.data(), b.size(), 0);
 }
 // --report with a *-fix mode: the -D values must be qualities the report can index
 inline void check_report_options(const Options& O, bool with_qual)

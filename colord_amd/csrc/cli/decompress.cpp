@@ -6,6 +6,7 @@
 #include "reader.hpp"
 #include "edits_stream.hpp"
 #include "overlaps_stream.hpp"
+#include "mappings_stream.hpp"
 #include "kspec_stream.hpp"
 #include "sketch_stream.hpp"
 #include <hip/hip_runtime.h>
@@ -113,10 +114,20 @@ int run_info(int argc, char** argv)
 {
 	bool want_report = false, want_edits = false, want_kspec = false, want_sketch = false, want_overlaps = false, names = false, json = false; std::vector<std::string> pos;
 	uint64_t min_block = 0; bool has_min_block = false;
+	bool want_mappings = false, summary = false; uint64_t coverage = 0;          // --mappings [--coverage W | --summary [--json]]
 	for (int i = 2; i < argc; ++i)
 	{
 		const std::string a = argv[i];
 		if (a == "--overlaps") want_overlaps = true;
+		else if (a == "--mappings") want_mappings = true;
+		else if (a == "--summary") summary = true;
+		else if (a == "--coverage")
+		{
+			char* end = nullptr;
+			if (i + 1 >= argc || !isdigit((unsigned char)argv[i + 1][0])) die("option --coverage needs a window length");
+			coverage = strtoull(argv[++i], &end, 10);
+			if (*end || !coverage) die("option --coverage needs a window length of one base or more");
+		}
 		else if (a == "--names") names = true;
 		else if (a == "--min-block")
 		{
@@ -128,9 +139,12 @@ int run_info(int argc, char** argv)
 		else if (a == "--report") want_report = true; else if (a == "--edit-profile") want_edits = true; else if (a == "--kmer-spectrum") want_kspec = true; else if (a == "--sketch") want_sketch = true; else if (a == "--json") json = true; else pos.push_back(a);
 	}
 	const int wanted = (want_report ? 1 : 0) + (want_edits ? 1 : 0) + (want_kspec ? 1 : 0) + (want_sketch ? 1 : 0);
-	if (pos.size() != 1 || (json && !wanted) || wanted + (want_overlaps ? 1 : 0) > 1 || ((names || has_min_block) && !want_overlaps))
+	const bool map_paf = want_mappings && !coverage && !summary;            // the three forms of --mappings: PAF (with --min-block, --names), --coverage W, --summary [--json]
+	if (pos.size() != 1 || (json && !wanted && !(want_mappings && summary)) || wanted + (want_overlaps ? 1 : 0) + (want_mappings ? 1 : 0) > 1 || ((names || has_min_block) && !want_overlaps && !map_paf) ||
+	    ((coverage || summary) && !want_mappings) || (coverage && summary))
 	{
-		fprintf(stderr, "usage: colord_hip info [--report [--json]] [--edit-profile [--json]] [--kmer-spectrum [--json]] archive.colord\n       colord_hip info --overlaps [--min-block N] [--names] archive.colord\n       colord_hip info --sketch [--json] archive.colord\n");
+		fprintf(stderr, "usage: colord_hip info [--report [--json]] [--edit-profile [--json]] [--kmer-spectrum [--json]] archive.colord\n       colord_hip info --overlaps [--min-block N] [--names] archive.colord\n"
+			"       colord_hip info --mappings [--min-block N] [--names] | --mappings --coverage W | --mappings --summary [--json] archive.colord\n       colord_hip info --sketch [--json] archive.colord\n");
 		return 1;
 	}
 	const std::string& path = pos[0];
@@ -174,6 +188,37 @@ int run_info(int argc, char** argv)
 			}
 		}
 		if (!print_paf(stdout, V, min_block, names ? &ids : nullptr)) die("the archive's `hipoverlaps` stream names a read the `header` stream does not hold");
+		return 0;
+	}
+	if (want_mappings)
+	{	// the stored read-to-genome records, on stdout, as PAF, as a coverage track or as a summary: `dna` and `qual` are not decoded, no GPU is used
+		uint64_t n_reads = 0;
+		if (summary)
+		{	// the reads of the archive, as `colord_hip info` prints them
+			std::vector<uint8_t> ib; uint64_t im = 0;
+			if (!ar.part(ar.id("info"), 0, ib, im) || ib.size() < 40) die("archive without a readable `info` stream");
+			try { n_reads = parse_info(ib).total_reads; } catch (const std::exception& e) { die(e.what()); }
+		}
+		ar.close();
+		MappingSet V; const int have = read_hipmappings(path, V);
+		if (have == 0) die("no mappings are stored in this archive (written without -G genome --mappings)");
+		if (have < 0) die("the archive's `hipmappings` stream is not one this build reads");
+		if (coverage) { print_mappings_coverage(stdout, V, coverage); return 0; }
+		if (summary) { print_mappings_summary(stdout, summarize_mappings(V, n_reads), json); return 0; }
+		std::vector<std::string> ids;
+		if (names)
+		{
+			HeaderCache H; H.decode_all(path);
+			if (!H.err.empty()) die("--names: " + H.err);
+			for (size_t i = 0; i + 1 < H.off.size(); ++i)
+			{	// a read's name: its id up to the first blank, or its index where no id is stored (-i none)
+				std::string id((const char*)H.ids.data() + H.off[i], (const char*)H.ids.data() + H.off[i + 1]);
+				const size_t cut = id.find_first_of(" \t");
+				if (cut != std::string::npos) id.resize(cut);
+				ids.push_back(id.empty() ? std::to_string(i) : id);
+			}
+		}
+		if (!print_mappings_paf(stdout, V, min_block, names ? &ids : nullptr)) die("the archive's `hipmappings` stream names a read the `header` stream does not hold");
 		return 0;
 	}
 	if (want_kspec)
@@ -228,6 +273,11 @@ int run_info(int argc, char** argv)
 	if (const int have = read_hipoverlaps(path, ovl); have > 0)
 		fprintf(stderr, "overlaps: %llu records of reads against reference reads (`colord_hip info --overlaps [--min-block N] [--names]` prints them as PAF)\n", (unsigned long long)ovl.recs.size());
 	else if (have < 0) fprintf(stderr, "overlaps: a `hipoverlaps` stream this build cannot read\n");
+	MappingSet mps;
+	if (const int have = read_hipmappings(path, mps); have > 0)
+		fprintf(stderr, "mappings: %llu records of reads against the %zu sequences of the reference genome (`colord_hip info --mappings [--min-block N] [--names]` prints them as PAF, `--mappings --coverage W` a coverage track, `--mappings --summary [--json]` what they add up to)\n",
+			(unsigned long long)mps.recs.size(), mps.seq_len.size());
+	else if (have < 0) fprintf(stderr, "mappings: a `hipmappings` stream this build cannot read\n");
 	return 0;
 }
 

@@ -46,6 +46,42 @@ inline Sequences read_fasta(const std::string& path)
 	return S;
 }
 
+// The names of the sequences read_fasta reads from the same file, indexed as it indexes them: the same walk over the lines (a `>` opens a
+// sequence at the start of the file and behind a sequence line only; one right behind a header line is sequence text to both), a sequence
+// with no kept base included.  A name is the header line behind its `>` up to the first blank.
+inline std::vector<std::string> read_fasta_names(const std::string& path)
+{
+	gzFile g = gzopen(path.c_str(), "rb");
+	if (!g) throw std::runtime_error("cannot open file: " + path);
+	gzbuffer(g, 1 << 22);
+	std::vector<uint8_t> buf(1 << 22);
+	std::vector<std::string> names; bool first = true, in_name = false;
+	enum { HEADER, SEQ, EOL_HEADER, EOL_SEQ } st = HEADER;
+	for (;;)
+	{
+		const int n = gzread(g, buf.data(), (unsigned)buf.size());
+		if (n < 0) { gzclose(g); throw std::runtime_error("read error (zlib): " + path); }
+		if (n == 0) break;
+		int i = 0;
+		if (first) { if (buf[0] != '>') { gzclose(g); throw std::runtime_error("wrong reference genome file format, multi fasta expected"); } first = false; names.emplace_back(); in_name = true; i = 1; }
+		for (; i < n; ++i)
+		{
+			const char c = (char)buf[i];
+			const bool eol = c == '\n' || c == '\r';
+			switch (st)
+			{
+			case HEADER: if (eol) st = EOL_HEADER; else if (in_name) { if (c == ' ' || c == '\t') in_name = false; else names.back().push_back(c); } break;
+			case SEQ: if (eol) st = EOL_SEQ; break;
+			case EOL_SEQ: if (eol) break; if (c == '>') { st = HEADER; names.emplace_back(); in_name = true; } else st = SEQ; break;
+			case EOL_HEADER: if (!eol) st = SEQ; break;
+			}
+		}
+	}
+	gzclose(g);
+	if (first) throw std::runtime_error("file " + path + " is empty");
+	return names;
+}
+
 // pieces of read_len bases, consecutive pieces overlapping by `overlap` (reference_genome.cpp:391-419)
 inline Sequences pseudo_reads(const Sequences& G, uint32_t read_len, uint32_t overlap)
 {

@@ -43,6 +43,7 @@ struct Options {
 	bool edit_profile = false;                      // --edit-profile: the edit-operation profile of the tuple streams (cl_ctx_set_edit_profile) in a `hipedits` stream
 	bool kmer_spectrum = false;                     // --kmer-spectrum: the count spectrum of the k-mers pass 1 counted (cl_ctx_set_kmer_spectrum) in a `hipkmers` stream
 	bool sketch = false; long sketch_size = -1, sketch_min_count = -1;   // --sketch [--sketch-size N] [--sketch-min-count M]: the MinHash sketch of the k-mers pass 1 counted at least M times (cl_ctx_set_kmer_sketch) in a `hipsketch` stream; defaults 10 000 and 2
+	bool mappings = false;                          // --mappings (with -G): the read-to-genome alignments the edit scripts hold (cl_ctx_set_mappings) in a `hipmappings` stream
 	bool overlaps = false;                          // --overlaps: the read-to-read overlaps the edit scripts hold (cl_ctx_set_overlaps) in a `hipoverlaps` stream
 	uint64_t qual_domain_symbols = 0;               // --qual-domain-symbols N: the quality models start afresh about every N symbols (cl_compressor_set_qual_domain_symbols; stream `hipqdomains`)
 	int gpus = 1; std::vector<int> gpu_list; std::string transport = "rccl";   // --gpus N [--gpu-list a,b,..] [--transport rccl|host]: reads sharded over N GPUs (run_compress_multi)
@@ -54,7 +55,7 @@ inline void usage()
 {
 	fprintf(stderr,
 		"usage: colord_hip compress-ont|compress-pbhifi|compress-pbraw [options] input.fastq|fasta[.gz] output.colord\n"
-		"       colord_hip decompress [--ignore-digest] [--gpu N] archive.colord output.fastq\n       colord_hip check [--gpu N] archive.colord\n       colord_hip info [--report [--json]] [--edit-profile [--json]] [--kmer-spectrum [--json]] archive.colord\n       colord_hip info --overlaps [--min-block N] [--names] archive.colord\n       colord_hip info --sketch [--json] archive.colord\n       colord_hip dist [--json] A.colord B.colord [C.colord ...]\n"
+		"       colord_hip decompress [--ignore-digest] [--gpu N] archive.colord output.fastq\n       colord_hip check [--gpu N] archive.colord\n       colord_hip info [--report [--json]] [--edit-profile [--json]] [--kmer-spectrum [--json]] archive.colord\n       colord_hip info --overlaps [--min-block N] [--names] archive.colord\n       colord_hip info --mappings [--min-block N] [--names] | --mappings --coverage W | --mappings --summary [--json] archive.colord\n       colord_hip info --sketch [--json] archive.colord\n       colord_hip dist [--json] A.colord B.colord [C.colord ...]\n"
 		"options (as the reference, arg_parse.cpp:455-640):\n"
 		"  -p,--priority ratio|balanced|memory   -k,--kmer-len K with -a,--anchor-len A (both or none)\n"
 		"  -q,--qual org|none|avg|2-fix|4-fix|5-fix|2-avg|4-avg|5-avg   -T,--qual-thresholds a,b,..   -D,--qual-values a,b,..\n"
@@ -132,6 +133,14 @@ inline void usage()
 		"                     Cost: one pass over the tuple bytes per chunk to count and one to fill; measured on an MI355X, 1 Gbase of synthetic ONT reads (64 156 reads): 12.2 + 12.9 ms of kernel\n"
 		"                     time next to 23.5 ms of --edit-profile and 962 ms of all kernels; 1.77 s from file to archive against 1.69 s without the option, inside the spread of three runs;\n"
 		"                     88 989 records, 4.3 MB, 1.1 percent of the archive (DESIGN.md 9)\n"
+		"  --mappings         with -G: the read-to-genome alignments that the edit scripts hold are stored in the archive (stream `hipmappings`, 48 bytes per record and the genome's sequence\n"
+		"                     names and lengths; the reference's decompressor ignores it): the genome's overlapping pieces are the first reference reads, and every stretch of a read's edit\n"
+		"                     script on ONE piece that holds an aligned column is one record, lifted on the device to the coordinates of the sequence the piece was cut from.\n"
+		"                     `colord_hip info --mappings [--min-block N] [--names] archive` prints them as PAF with the FASTA's sequence names, `info --mappings --coverage W` a bedGraph\n"
+		"                     track of the mean depth in windows of W bases, `info --mappings --summary [--json]` what they add up to; none decodes `dna` or `qual` or needs a GPU.\n"
+		"                     WHAT IT IS NOT: A READ CODED AGAINST EARLIER READS INSTEAD OF GENOME PIECES YIELDS NO RECORD, AND A READ THAT SPANS A PIECE BOUNDARY YIELDS ONE RECORD PER\n"
+		"                     PIECE; THESE ARE NOT STITCHED.  `decompress` / `check` ignore the stream.  Works with --stream-input, --part-symbols, --chunk-bases and every other view.\n"
+		"                     Not without -G, not with --gpus > 1, --domains > 1 or --overlaps.  Cost: the walk of --overlaps and 48 bytes read and written per record (DESIGN.md 4m, 9)\n"
 		"  --qual-domain-symbols N   model domains of the QUALITY stream alone: its adaptive models start afresh at the first part boundary at which a domain holds N coded\n"
 		"                     symbols, and the starts are recorded (stream `hipqdomains`).  `colord_hip decompress --gpu N` / `check --gpu N` then decode the domains side by\n"
 		"                     side on the device, one lane each; without --gpu they decode on the host as one chain that starts afresh at every domain.  The k-mer set, the\n"
@@ -204,6 +213,7 @@ inline Options parse_options(int argc, char** argv)
 		else if (a == "--sketch-size") { O.sketch_size = atol(need(i).c_str()); if (O.sketch_size < 1 || O.sketch_size > (1l << 20)) die("--sketch-size must be in [1, 1048576]"); }
 		else if (a == "--sketch-min-count") { O.sketch_min_count = atol(need(i).c_str()); if (O.sketch_min_count < 1 || O.sketch_min_count > 0x7fffffffl) die("--sketch-min-count must be in [1, 2147483647]"); }
 		else if (a == "--overlaps") O.overlaps = true;
+		else if (a == "--mappings") O.mappings = true;
 		else if (a == "--parse-threads") { O.parse_threads = atoi(need(i).c_str()); if (O.parse_threads < 1 || O.parse_threads > 256) die("--parse-threads must be in [1, 256]"); }
 		else if (a == "-h" || a == "--help") { usage(); exit(0); }
 		else if (!a.empty() && a[0] == '-' && a.size() > 1) die("unknown option " + a);
@@ -239,6 +249,13 @@ inline Options parse_options(int argc, char** argv)
 	}
 	if (!O.sketch && (O.sketch_size >= 0 || O.sketch_min_count >= 0)) { usage(); die("--sketch-size and --sketch-min-count need --sketch"); }
 	if (O.sketch) { if (O.sketch_size < 0) O.sketch_size = 10000; if (O.sketch_min_count < 0) O.sketch_min_count = 2; }
+	if (O.mappings)
+	{	// a record's target is a piece of the reference genome, lifted by ONE geometry on ONE device
+		if (O.genome.empty()) die("--mappings needs a reference genome (-G): its records are alignments against the genome's pieces");
+		if (O.gpus > 1) die("--mappings is not available with --gpus > 1 (the records of the ranks are not merged yet)");
+		if (O.domains > 1) die("--mappings is not available with --domains > 1 (every domain is a compressor of its own)");
+		if (O.overlaps) die("--mappings is not available with --overlaps (which refuses -G)");
+	}
 	if (O.overlaps)
 	{	// a record names reads of the input: every reference id must be one of them, in ONE set of reference reads
 		if (O.gpus > 1) die("--overlaps is not available with --gpus > 1 (the ranks' reference ids are not translated to reads of the input yet)");

@@ -362,6 +362,9 @@ struct cl_ctx {
 	bool overlaps = false;                       // cl_ctx_set_overlaps: tuple_streams (pass_steps.hpp) keeps the overlap records of every batch it makes (overlaps.hip)
 	std::map<uint64_t, std::vector<cl_overlap>> overlap_recs;   // the records of the batches made on THIS context by the batch's first read (under overlaps_mu: cl_ctx_overlaps merges the encode lanes')
 	mutable std::mutex overlaps_mu;
+	bool mappings = false;                       // cl_ctx_set_mappings: tuple_streams (pass_steps.hpp) keeps the lifted records of every batch on genome pieces (mappings.hip)
+	std::map<uint64_t, std::vector<cl_overlap>> mapping_recs;   // ... by the batch's first read (under mappings_mu: cl_ctx_mappings merges the encode lanes')
+	mutable std::mutex mappings_mu;
 	uint64_t gap_paths[11] = { 0 };              // cl_ctx_gap_paths: the last cl_encode_reads' gaps per size class 0..7, quad -> wave, giant -> wave, wave-pool redo rounds (owner thread only)
 	std::map<std::string, KernelTime> times;     // per-kernel accumulated HIP-event time of the last API call
 	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;

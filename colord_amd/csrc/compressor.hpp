@@ -2,6 +2,7 @@
 // exchanges of sharded reads); lookahead.hip is the pipeline that works on announced chunks ahead of the calls that code them.
 #pragma once
 #include "pass_steps.hpp"
+#include "mappings.hpp"
 
 // An announced chunk on its way through the look-ahead: stage A by an encode lane, then the coders' model-independent halves.
 struct Prepared : TupleStreams {
@@ -69,6 +70,8 @@ struct cl_compressor {
 	std::vector<DevBuf<uint32_t>> bounds;           // per chunk: n_reads + 1, reference reads before each read
 	cl_reads* refs = nullptr; cl_index* index = nullptr; uint32_t ref_base = 0, n_refs_total = 0;
 	DevBuf<uint32_t> ref_read;                      // cl_ctx_set_overlaps: reference id -> index of that read in the input (n_refs_total entries), made in refs_finish
+	DevBuf<uint64_t> map_seq_len; DevBuf<uint32_t> map_piece_first; // cl_compressor_genome_geometry: the tables of the pseudo reads' geometry (mappings.hpp) ...
+	MapGeom map_geom{}; bool has_map_geom = false;  // ... and the geometry over them, for the lifts of cl_ctx_set_mappings
 	cl_dna_coder* dna = nullptr; cl_qual_coder* qual = nullptr;
 	uint64_t qual_domain_symbols = 0;               // cl_compressor_set_qual_domain_symbols: handed to the quality coder when it is created
 	// pass 2b

@@ -37,6 +37,7 @@ template<class Work> static cl_status work_on(cl_compressor* c, cl_ctx* ctx, Wor
 	ctx->verify = c->ctx->verify;
 	ctx->edit_profile = c->ctx->edit_profile;
 	ctx->overlaps = c->ctx->overlaps;
+	ctx->mappings = c->ctx->mappings;
 	const cl_status s = work();
 	cl_timing_collect(ctx);
 	return s;

@@ -75,6 +75,12 @@ cl_status kmer_sketch_range(cl_ctx* ctx, const uint64_t* d_keys, const uint32_t*
 cl_status overlaps_chunk(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, const uint32_t* d_ref_read, uint32_t n_ref_read);
 // ... and that table's entries of one chunk: read i (input index first_read + i) is reference d_bounds[i] iff d_bounds[i + 1] > d_bounds[i] (n + 1 bounds)
 cl_status overlaps_ref_reads(cl_ctx* ctx, const uint32_t* d_bounds, uint32_t n, uint32_t first_read, uint32_t* d_ref_read, uint32_t n_ref_read);
+// ... and the records alone, ids untranslated, in a buffer made by the call (mappings.hip lifts them)
+cl_status overlaps_records(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, DevBuf<cl_overlap>& out, uint64_t* n_out);
+// mappings.hip (cl_ctx_set_mappings): the records of a batch whose target is a piece of the reference genome, lifted to the genome's sequences
+// (geom: mappings.hpp, tables on the device; null is an error) and kept on the host by the context that made them
+struct MapGeom;
+cl_status mappings_chunk(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, const MapGeom* geom);
 const cl_qual_params* cl_qual_coder_params(const cl_qual_coder* q);     // qual.hip: the parameters the coder was created with
 
 // the DNA coder's state-independent half ahead of time (dna.hip): lookahead.hip walks the NEXT chunk's tuples from the hook that

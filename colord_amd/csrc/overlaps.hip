@@ -277,6 +277,11 @@ cl_status overlaps_chunk(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es,
 	ctx->overlap_recs[first_read] = std::move(h);
 	return CL_OK;
 }
+// Internal (mappings.hip): the records of one batch with no translation table (`t` is the stream's reference id), in a buffer made here
+cl_status overlaps_records(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, DevBuf<cl_overlap>& out, uint64_t* n_out)
+{
+	return ov_run(ctx, refs, d_es, d_es_off, n_reads, first_read, nullptr, 0, 0, nullptr, 0, &out, n_out);
+}
 // Internal (stream.hip, driver.hip): the reference id -> read index table of one chunk's `bounds` (n + 1 entries) scattered into d_ref_read
 cl_status overlaps_ref_reads(cl_ctx* ctx, const uint32_t* d_bounds, uint32_t n, uint32_t first_read, uint32_t* d_ref_read, uint32_t n_ref_read)
 {

@@ -335,6 +335,12 @@ extern "C" cl_status cl_compressor_refs_finish(cl_compressor* c)
 		for (size_t i = 0; i < c->bounds.size(); ++i) { if (nr) CL_TRY(overlaps_ref_reads(ctx, c->bounds[i].p, c->chunk_reads[i], (uint32_t)g, c->ref_read.p, nr)); g += c->chunk_reads[i]; }
 		HIP_TRY(ctx, hipStreamSynchronize(cl_launch_stream(ctx)));
 	}
+	if (ctx->mappings)
+	{	// a record's target is a piece of the genome, lifted by the geometry: one rank, pseudo reads, and the geometry they were cut by
+		if (c->world > 1) return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_ctx_set_mappings: not with reads sharded over ranks (the records of the ranks are not merged yet)");
+		if (!c->n_pseudo) return cl_fail(ctx, CL_E_INVALID, "cl_ctx_set_mappings: needs the pseudo reads of a reference genome (cl_compressor_pseudo_reads)");
+		if (!c->has_map_geom) return cl_fail(ctx, CL_E_INVALID, "cl_ctx_set_mappings: needs the geometry of the pseudo reads (cl_compressor_genome_geometry)");
+	}
 	uint64_t n_pairs = c->pair_ids.n;
 	if (c->world > 1) CL_TRY(gather_refs(c, pk, iv, ln, words, nr, n_pairs));
 	CL_TRY(cl_reads_from_arena(ctx, pk.p, iv.p, ln.p, nr, &c->refs));
@@ -361,7 +367,7 @@ cl_status compressor_tuple_streams(cl_compressor* c, cl_ctx* ctx, size_t idx, co
 	Handle<cl_kmer_lists, cl_kmer_lists_free> lists;            // a4: accepted k-mers per read
 	CL_TRY(cl_accepted_kmers(ctx, c->kset, reads, c->P.k, c->P.f, lists.out()));
 	uint64_t g = c->first_read; for (size_t i = 0; i < idx; ++i) g += c->chunk_reads[i];      // the chunk's first read in the whole input
-	return tuple_streams(ctx, &c->P, lists, c->index, c->refs, reads, c->bounds[idx].p, h_pack_bounds, n_packs, g, c->ref_read.p, c->ref_read.p ? c->n_refs_total : 0u, out);
+	return tuple_streams(ctx, &c->P, lists, c->index, c->refs, reads, c->bounds[idx].p, h_pack_bounds, n_packs, g, c->ref_read.p, c->ref_read.p ? c->n_refs_total : 0u, c->has_map_geom ? &c->map_geom : nullptr, out);
 }
 
 extern "C" cl_status cl_compressor_encode(cl_compressor* c, const cl_reads* reads, const uint8_t* d_quals, const uint64_t* d_base_off,

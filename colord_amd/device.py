@@ -59,7 +59,8 @@ class _OrderedLib:
                   "cl_edits_clear", "cl_edits_add", "cl_edit_profile_host", "cl_edit_profile_error", "cl_ctx_set_edit_profile", "cl_ctx_edit_profile", "cl_compressor_edit_profile",
                   "cl_kspec_clear", "cl_kspec_add", "cl_ctx_set_kmer_spectrum", "cl_ctx_kmer_spectrum", "cl_compressor_kmer_spectrum",
                   "cl_sketch_hash", "cl_sketch_create", "cl_sketch_info", "cl_sketch_entries", "cl_sketch_merge", "cl_ctx_set_kmer_sketch", "cl_ctx_kmer_sketch", "cl_compressor_kmer_sketch",
-                  "cl_overlaps_host", "cl_ctx_set_overlaps", "cl_ctx_overlaps", "cl_compressor_overlaps")
+                  "cl_overlaps_host", "cl_ctx_set_overlaps", "cl_ctx_overlaps", "cl_compressor_overlaps",
+                  "cl_mappings_lift_host", "cl_ctx_set_mappings", "cl_ctx_mappings", "cl_compressor_mappings")
 
     def __init__(self, lib, device):
         self._lib, self._device, self._cache = lib, device, {}
@@ -249,6 +250,34 @@ class Context:
             cap = need.value
         out = torch.empty((cap, 12), dtype=torch.int32, device=self.device)
         _check(self, self.lib.cl_overlaps_of(*args, out.data_ptr() if cap else None, cap, C.byref(need)))
+        return out[:need.value]
+
+    def set_mappings(self, on: bool = True):
+        """cl_ctx_set_mappings: every batch of tuple streams made by a compressor of this context (one with pseudo reads and their geometry)
+        leaves its records on genome pieces, lifted to the genome's sequences (dropped when switched on)."""
+        self.lib.cl_ctx_set_mappings(self.h, int(bool(on)))
+
+    def mappings(self) -> np.ndarray:
+        """cl_ctx_mappings: the lifted records so far of this context and its compressor's encode lanes in input order, (n, 12) uint32 in the
+        field order of cl_overlap."""
+        return _overlap_records(self.lib.cl_ctx_mappings, self.h)
+
+    def mappings_lift(self, recs: torch.Tensor, seq_len, read_len: int, overlap: int, cap: "int | None" = None) -> torch.Tensor:
+        """cl_mappings_lift: the (n, 12) int32 records on the device whose target is a genome piece, lifted to the sequences of seq_len (host),
+        (m, 12) int32 on the device.  With cap the call is made once with room for cap records (CL_E_CAPACITY raises); without, the need is
+        asked for first.  A refused record raises (CL_E_INVALID, the text names the first)."""
+        recs = recs.contiguous()
+        n = recs.numel() // 12
+        sl = np.ascontiguousarray(np.asarray(seq_len, dtype=np.uint64))
+        args = (self.h, recs.data_ptr() if n else None, n, sl.ctypes.data if len(sl) else None, len(sl), read_len, overlap)
+        need = C.c_uint64(0)
+        if cap is None:
+            st = self.lib.cl_mappings_lift(*args, None, 0, C.byref(need))
+            if st not in (N.CL_OK, N.CL_E_CAPACITY):
+                _check(self, st)
+            cap = need.value
+        out = torch.empty((cap, 12), dtype=torch.int32, device=self.device)
+        _check(self, self.lib.cl_mappings_lift(*args, out.data_ptr() if cap else None, cap, C.byref(need)))
         return out[:need.value]
 
     def set_kmer_spectrum(self, on: bool = True):
@@ -928,6 +957,16 @@ class Compressor(_Obj):
 
     def pseudo_reads(self, pseudo: "Reads"):
         _check(self.ctx, self.ctx.lib.cl_compressor_pseudo_reads(self.h, pseudo.h))
+
+    def genome_geometry(self, seq_len, read_len: int, overlap: int):
+        """cl_compressor_genome_geometry: the geometry the pseudo reads were cut by (Context.set_mappings lifts with it); one that does not
+        give exactly the pseudo reads raises (CL_E_INVALID)."""
+        sl = np.ascontiguousarray(np.asarray(seq_len, dtype=np.uint64))
+        _check(self.ctx, self.ctx.lib.cl_compressor_genome_geometry(self.h, sl.ctypes.data if len(sl) else None, len(sl), read_len, overlap))
+
+    def mappings(self) -> np.ndarray:
+        """cl_compressor_mappings: the lifted records of the chunks whose tuple streams are made (Context.set_mappings), in input order."""
+        return _overlap_records(self.ctx.lib.cl_compressor_mappings, self.h)
 
     def prepare(self, reads: "Reads", pack_bounds, part_bounds=None, quals: torch.Tensor | None = None, base_off: torch.Tensor | None = None):
         """cl_compressor_prepare[_parts]: announce a chunk of a later encode() call; its candidates / anchors / edit scripts are

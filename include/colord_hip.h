@@ -597,6 +597,39 @@ cl_status cl_overlaps_host(const uint8_t* h_ref_codes, const uint64_t* h_ref_off
 void cl_ctx_set_overlaps(cl_ctx* ctx, int on);
 cl_status cl_ctx_overlaps(const cl_ctx* ctx, cl_overlap* h_out, uint64_t cap, uint64_t* n_out);
 
+/* ---- read-to-genome mappings (no counterpart in the reference) — what a reference-genome run aligned, per read ------- */
+/* With a reference genome the overlapping pieces of its sequences (the pseudo reads) are reference ids 0 .. n_pseudo-1, and a cl_overlap
+ * whose `t` is such an id is an alignment of the read against a PIECE of the genome.  The LIFT moves it to the genome's sequences.
+ * Geometry: n_seqs sequences of seq_len[s] bases, pieces of read_len bases every step = read_len - overlap bases; sequence s has
+ * ceil(seq_len[s] / step) pieces (none when it has no base), piece p of it starts at p * step and is min(read_len, seq_len[s] - start)
+ * long; the pieces of the sequences follow each other, so n_pseudo is their sum.  A record with t >= n_pseudo targets a read of the
+ * input and is DROPPED; one with t < n_pseudo is kept: t = the sequence, tlen = its length, ts and te grow by the piece's start, flags
+ * gets bit 2 (a target in genome coordinates), every other field stays.  The kept records stay in their order.
+ * WHAT IT IS NOT: a read coded against earlier reads instead of genome pieces yields no record, and a read that spans a piece boundary
+ * yields one record per piece; these are not stitched.
+ * cl_mappings_lift: the n records at d_recs (device, at a multiple of 16 bytes, as cl_overlaps_of leaves them without a translation
+ * table) into d_out (device, cap records); the geometry's lengths are on the host.  On the device (k_map_lift): a lane per record, one
+ * pass flags, a prefix sum places, the same kernel body fills.  *n_out = the kept records.  cap too small (or d_out null):
+ * CL_E_CAPACITY, *n_out holds the need and nothing was written.  A kept record whose tlen is not its piece's length (code 1), with a
+ * lifted position past 2^32 - 1 (code 2) or with te lifted past the sequence's end (code 3) is CL_E_INVALID, the text naming the first
+ * such record; *n_out = 0 and nothing is handed out.  read_len <= overlap is CL_E_INVALID; a sequence of 2^32 bases or more, and 2^32
+ * pieces or records or more, CL_E_UNSUPPORTED. */
+cl_status cl_mappings_lift(cl_ctx* ctx, const cl_overlap* d_recs, uint64_t n, const uint64_t* h_seq_len, uint32_t n_seqs, uint32_t read_len, uint32_t overlap,
+                           cl_overlap* d_out, uint64_t cap, uint64_t* n_out);
+/* The same on the HOST, the same checks in the same order; h_out may be null to ask for the count.  bad_record / bad_code (optional):
+ * the first refused record and its code. */
+cl_status cl_mappings_lift_host(const cl_overlap* h_recs, uint64_t n, const uint64_t* h_seq_len, uint32_t n_seqs, uint32_t read_len, uint32_t overlap,
+                                cl_overlap* h_out, uint64_t cap, uint64_t* n_out, uint64_t* bad_record, uint32_t* bad_code);
+/* Opt-in (off by default: one flag test per batch, no launch, no allocation, every output byte the same).  While it is on, every batch
+ * of tuple streams made by cl_compressor_encode, or by an encode lane of a compressor created on this context, leaves its lifted records
+ * on the host (the walk of cl_overlaps_of, then the lift).  cl_ctx_mappings: those of this context and its compressor's lanes so far, in
+ * input order (h_out, cap records; CL_E_CAPACITY with *n_out = the need and nothing written when cap is too small); switching the flag
+ * on drops what was kept.  cl_compressor_refs_finish refuses a compressor without pseudo reads or without their geometry
+ * (cl_compressor_genome_geometry; CL_E_INVALID) and one that shares its reads with other ranks (CL_E_UNSUPPORTED); cl_compress_shard
+ * has no pseudo reads and refuses the flag (CL_E_UNSUPPORTED).  Independent of cl_ctx_set_overlaps. */
+void cl_ctx_set_mappings(cl_ctx* ctx, int on);
+cl_status cl_ctx_mappings(const cl_ctx* ctx, cl_overlap* h_out, uint64_t cap, uint64_t* n_out);
+
 /* ---- a14 + a16: CDNACoder / CEntrComprReads (dna_coder.{h,cpp}, entr_read.h:56-80) --------------------- */
 typedef struct cl_dna_coder cl_dna_coder;
 /* CDNACoder::Init(true, maxCandidates, level, ., n_ref_genome_pseudo_reads): one adaptive model set that
@@ -767,6 +800,12 @@ cl_status cl_compressor_kmer_spectrum(const cl_compressor* c, cl_kspec* out);
 cl_status cl_compressor_kmer_sketch(const cl_compressor* c, cl_sketch* out);
 /* cl_ctx_overlaps of the compressor's context (cl_ctx_set_overlaps): after the last cl_compressor_encode, of every chunk */
 cl_status cl_compressor_overlaps(const cl_compressor* c, cl_overlap* h_out, uint64_t cap, uint64_t* n_out);
+/* The geometry of the pseudo reads (cl_mappings_lift), for cl_ctx_set_mappings: once, behind cl_compressor_pseudo_reads and before
+ * cl_compressor_refs_finish.  The piece count and every piece length are made again from it; a geometry that does not give the
+ * compressor's n_pseudo pseudo reads with exactly their lengths is refused (CL_E_INVALID).  The tables stay on the device. */
+cl_status cl_compressor_genome_geometry(cl_compressor* c, const uint64_t* h_seq_len, uint32_t n_seqs, uint32_t read_len, uint32_t overlap);
+/* cl_ctx_mappings of the compressor's context (cl_ctx_set_mappings): after the last cl_compressor_encode, of every chunk */
+cl_status cl_compressor_mappings(const cl_compressor* c, cl_overlap* h_out, uint64_t cap, uint64_t* n_out);
 
 /* cl_qual_coder_set_domain_symbols / cl_qual_coder_domains of the compressor's quality coder.  The setting must be made before the
  * first cl_compressor_encode or cl_compressor_prepare_parts call (CL_E_INVALID afterwards, and without a quality stream); the `dna`
