@@ -68,6 +68,15 @@ class Edits(C.Structure):
     as_dict = Report.as_dict
 
 
+class PileupSums(C.Structure):
+    """cl_pileup_sums: the totals of a pileup table."""
+    _fields_ = [("covered", C.c_uint64), ("match", C.c_uint64), ("sub", C.c_uint64), ("del_", C.c_uint64), ("ins", C.c_uint64), ("ins_unplaced", C.c_uint64), ("reads", C.c_uint64)]
+    NAMES = ("covered", "match", "sub", "del", "ins", "ins_unplaced", "reads")
+
+    def as_dict(self):
+        return {k: int(getattr(self, f[0])) for k, f in zip(self.NAMES, self._fields_)}
+
+
 KSPEC_EXACT = 4096
 class KSpec(C.Structure):
     """cl_kspec: the k-mer count spectrum; every field adds over disjoint key ranges except max_count (max)."""
@@ -236,6 +245,18 @@ _SIG = {
     "cl_ctx_mappings": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cl_compressor_mappings": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cl_compressor_genome_geometry": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "cl_pileup_create": (C.c_int32, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "cl_pileup_free": (None, [_P]),
+    "cl_pileup_positions": (C.c_uint64, [_P]),
+    "cl_pileup_add": (C.c_int32, [_P, _P, _P, _P, C.c_uint32, C.c_uint32]),
+    "cl_pileup_finish": (C.c_int32, [_P]),
+    "cl_pileup_columns": (C.c_int32, [_P, C.c_uint64, C.c_uint64, _P]),
+    "cl_pileup_sites": (C.c_int32, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cl_pileup_totals": (C.c_int32, [_P, C.POINTER(PileupSums)]),
+    "cl_pileup_host": (C.c_int32, [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, C.c_uint64,
+                                   C.POINTER(C.c_uint64), C.POINTER(PileupSums), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "cl_ctx_set_pileup": (None, [_P, C.c_int]),
+    "cl_compressor_pileup": (C.c_int32, [_P, C.POINTER(_P)]),
     "cl_digest_bases": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(Digest)]),
     "cl_digest_quals": (C.c_int32, [_P, C.POINTER(QualParams), _P, _P, _P, C.c_uint64, C.POINTER(Digest)]),
     "cl_digest_bases_host": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(Digest)]),

@@ -208,6 +208,7 @@ int run_compress(int argc, char** argv)
 	if (O.sketch) ck(ctx, cl_ctx_set_kmer_sketch(ctx, 1, (uint32_t)O.sketch_size, (uint32_t)O.sketch_min_count), "cl_ctx_set_kmer_sketch");
 	if (O.overlaps) cl_ctx_set_overlaps(ctx, 1);
 	if (O.mappings) cl_ctx_set_mappings(ctx, 1);
+	if (O.pileup) cl_ctx_set_pileup(ctx, 1);
 	std::vector<uint64_t> report_lens;                         // --report: every read length, as the reader hands the reads over in pass 1 (N50 / N90)
 	ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, nullptr, estimated_bases(R), &cmp), "cl_compressor_create");
 	if (O.qual_domain_symbols)
@@ -253,7 +254,7 @@ int run_compress(int argc, char** argv)
 	{
 		GM.add_pseudo_reads(ctx, cmp, k);
 		if (O.verbose) fprintf(stderr, "# ref genome pseudo reads: %u (length %u, overlap %u)\n", GM.n_pseudo, GM.read_len, GM.overlap);
-		if (O.mappings)
+		if (O.mappings || O.pileup)
 		{	// the geometry the pieces were cut by: the library makes them again from it and refuses what does not give exactly the pseudo reads
 			const std::vector<uint64_t> sl = GM.seq_lens();
 			ck(ctx, cl_compressor_genome_geometry(cmp, sl.data(), (uint32_t)sl.size(), GM.read_len, GM.overlap), "cl_compressor_genome_geometry");
@@ -386,6 +387,13 @@ int run_compress(int argc, char** argv)
 		if (nv) ck(ctx, cl_compressor_mappings(cmp, V.recs.data(), nv, &nv), "cl_compressor_mappings");
 		add_mappings(ar, V, GM, O.genome, n);
 		if (O.verbose) fprintf(stderr, "# mappings: %llu records on %zu sequences\n", (unsigned long long)nv, V.seq_len.size());
+	}
+	if (O.pileup)
+	{
+		PileupSet V;
+		add_pileup(ar, ctx, cmp, V, O, GM);
+		if (O.verbose) fprintf(stderr, "# pileup: %llu sites on %zu sequences, %llu positions with an aligned column, %llu reads on genome pieces\n", (unsigned long long)V.sites.size(), V.seq_len.size(),
+			(unsigned long long)V.sums.covered, (unsigned long long)V.sums.reads);
 	}
 	if (O.qual_domain_symbols)
 	{

@@ -11,6 +11,7 @@
 #include "edits_stream.hpp"
 #include "overlaps_stream.hpp"
 #include "mappings_stream.hpp"
+#include "pileup_stream.hpp"
 #include "kspec_stream.hpp"
 #include "sketch_stream.hpp"
 #include <ctime>
@@ -374,6 +375,26 @@ inline void add_mappings(ArchiveWriter& ar, MappingSet& S, const GenomeMode& GM,
 	for (const cl_overlap& o : S.recs) if (o.q >= n_reads || o.t >= S.seq_len.size() || o.te > S.seq_len[o.t] || !(o.flags & OV_GENOME)) die("internal: a mapping record names a read outside the input or lies outside its sequence");
 	const std::vector<uint8_t> b = S.pack();
 	ar.add(ar.reg("hipmappings"), b.data(), b.size(), 0);
+}
+// --pileup: the `hippileup` stream (pileup_stream.hpp), before finish_archive: the geometry, the thresholds, the totals of the compressor's table, the genome's
+// sequence names and lengths, and the table's sites — the table itself is the size of the genome and stays on the device
+inline uint32_t pileup_permille(double frac) { return (uint32_t)(frac * 1000.0 + 0.5); }
+inline void add_pileup(ArchiveWriter& ar, cl_ctx* ctx, cl_compressor* cmp, PileupSet& S, const Options& O, const GenomeMode& GM)
+{
+	cl_pileup* p = nullptr; uint64_t n = 0;
+	ck(ctx, cl_compressor_pileup(cmp, &p), "cl_compressor_pileup");
+	S.read_len = GM.read_len; S.overlap = GM.overlap; S.seq_len = GM.seq_lens();
+	S.thr = PileThresholds{ (uint32_t)O.pileup_min_depth, (uint32_t)O.pileup_min_alt, pileup_permille(O.pileup_min_frac) };
+	try { S.names = genome_io::read_fasta_names(O.genome); } catch (const std::exception& e) { die(e.what()); }
+	if (S.names.size() != S.seq_len.size()) die("internal: the reference genome has " + std::to_string(S.seq_len.size()) + " sequences and " + std::to_string(S.names.size()) + " names");
+	ck(ctx, cl_pileup_totals(p, &S.sums), "cl_pileup_totals");
+	const cl_status s = cl_pileup_sites(p, S.thr.min_depth, S.thr.min_alt, S.thr.min_permille, nullptr, 0, &n);
+	if (s != CL_OK && s != CL_E_CAPACITY) ck(ctx, s, "cl_pileup_sites");
+	S.sites.resize(n);
+	if (n) ck(ctx, cl_pileup_sites(p, S.thr.min_depth, S.thr.min_alt, S.thr.min_permille, S.sites.data(), n, &n), "cl_pileup_sites");
+	for (const cl_pileup_site& o : S.sites) if (o.seq >= S.seq_len.size() || o.pos >= S.seq_len[o.seq]) die("internal: a pileup site lies outside its sequence");
+	const std::vector<uint8_t> b = S.pack();
+	ar.add(ar.reg("hippileup"), b.data(), b.size(), 0);
 }
 // --report with a *-fix mode: the -D values must be qualities the report can index
 inline void check_report_options(const Options& O, bool with_qual)

@@ -7,6 +7,7 @@
 #include "edits_stream.hpp"
 #include "overlaps_stream.hpp"
 #include "mappings_stream.hpp"
+#include "pileup_stream.hpp"
 #include "kspec_stream.hpp"
 #include "sketch_stream.hpp"
 #include <hip/hip_runtime.h>
@@ -115,10 +116,27 @@ int run_info(int argc, char** argv)
 	bool want_report = false, want_edits = false, want_kspec = false, want_sketch = false, want_overlaps = false, names = false, json = false; std::vector<std::string> pos;
 	uint64_t min_block = 0; bool has_min_block = false;
 	bool want_mappings = false, summary = false; uint64_t coverage = 0;          // --mappings [--coverage W | --summary [--json]]
+	bool want_pileup = false, vcf = false, has_min_alt = false, has_min_frac = false; uint64_t min_alt = 0; double min_frac = 0;      // --pileup [--min-alt N] [--min-frac F] [--vcf] | --pileup --summary [--json]
 	for (int i = 2; i < argc; ++i)
 	{
 		const std::string a = argv[i];
 		if (a == "--overlaps") want_overlaps = true;
+		else if (a == "--pileup") want_pileup = true;
+		else if (a == "--vcf") vcf = true;
+		else if (a == "--min-alt")
+		{
+			char* end = nullptr;
+			if (i + 1 >= argc || !isdigit((unsigned char)argv[i + 1][0])) die("option --min-alt needs a number");
+			min_alt = strtoull(argv[++i], &end, 10); has_min_alt = true;
+			if (*end) die("option --min-alt needs a number");
+		}
+		else if (a == "--min-frac")
+		{
+			char* end = nullptr;
+			if (i + 1 >= argc || !argv[i + 1][0]) die("option --min-frac needs a fraction in [0, 1]");
+			min_frac = strtod(argv[++i], &end); has_min_frac = true;
+			if (*end || !(min_frac >= 0 && min_frac <= 1)) die("option --min-frac needs a fraction in [0, 1]");
+		}
 		else if (a == "--mappings") want_mappings = true;
 		else if (a == "--summary") summary = true;
 		else if (a == "--coverage")
@@ -140,11 +158,13 @@ int run_info(int argc, char** argv)
 	}
 	const int wanted = (want_report ? 1 : 0) + (want_edits ? 1 : 0) + (want_kspec ? 1 : 0) + (want_sketch ? 1 : 0);
 	const bool map_paf = want_mappings && !coverage && !summary;            // the three forms of --mappings: PAF (with --min-block, --names), --coverage W, --summary [--json]
-	if (pos.size() != 1 || (json && !wanted && !(want_mappings && summary)) || wanted + (want_overlaps ? 1 : 0) + (want_mappings ? 1 : 0) > 1 || ((names || has_min_block) && !want_overlaps && !map_paf) ||
-	    ((coverage || summary) && !want_mappings) || (coverage && summary))
+	if (pos.size() != 1 || (json && !wanted && !((want_mappings || want_pileup) && summary)) || wanted + (want_overlaps ? 1 : 0) + (want_mappings ? 1 : 0) + (want_pileup ? 1 : 0) > 1 ||
+	    ((names || has_min_block) && !want_overlaps && !map_paf) || (coverage && !want_mappings) || (summary && !want_mappings && !want_pileup) || (coverage && summary) ||
+	    ((vcf || has_min_alt || has_min_frac) && (!want_pileup || summary)))
 	{
 		fprintf(stderr, "usage: colord_hip info [--report [--json]] [--edit-profile [--json]] [--kmer-spectrum [--json]] archive.colord\n       colord_hip info --overlaps [--min-block N] [--names] archive.colord\n"
-			"       colord_hip info --mappings [--min-block N] [--names] | --mappings --coverage W | --mappings --summary [--json] archive.colord\n       colord_hip info --sketch [--json] archive.colord\n");
+			"       colord_hip info --mappings [--min-block N] [--names] | --mappings --coverage W | --mappings --summary [--json] archive.colord\n"
+			"       colord_hip info --pileup [--min-alt N] [--min-frac F] [--vcf] | --pileup --summary [--json] archive.colord\n       colord_hip info --sketch [--json] archive.colord\n");
 		return 1;
 	}
 	const std::string& path = pos[0];
@@ -221,6 +241,16 @@ int run_info(int argc, char** argv)
 		if (!print_mappings_paf(stdout, V, min_block, names ? &ids : nullptr)) die("the archive's `hipmappings` stream names a read the `header` stream does not hold");
 		return 0;
 	}
+	if (want_pileup)
+	{	// the stored sites of the per-position base counts, on stdout, as a table, as a VCF or as a summary: nothing is decoded, no GPU is used
+		ar.close();
+		PileupSet V; const int have = read_hippileup(path, V);
+		if (have == 0) die("no pileup is stored in this archive (written without -G genome --pileup)");
+		if (have < 0) die("the archive's `hippileup` stream is not one this build reads");
+		const uint64_t permille = (uint64_t)(min_frac * 1000.0 + 0.5);
+		if (summary) print_pileup_summary(stdout, V, json); else if (vcf) print_pileup_vcf(stdout, V, min_alt, permille); else print_pileup_table(stdout, V, min_alt, permille);
+		return 0;
+	}
 	if (want_kspec)
 	{	// the stored k-mer count spectrum alone, on stdout: nothing is decoded
 		ar.close();
@@ -278,6 +308,11 @@ int run_info(int argc, char** argv)
 		fprintf(stderr, "mappings: %llu records of reads against the %zu sequences of the reference genome (`colord_hip info --mappings [--min-block N] [--names]` prints them as PAF, `--mappings --coverage W` a coverage track, `--mappings --summary [--json]` what they add up to)\n",
 			(unsigned long long)mps.recs.size(), mps.seq_len.size());
 	else if (have < 0) fprintf(stderr, "mappings: a `hipmappings` stream this build cannot read\n");
+	PileupSet pil;
+	if (const int have = read_hippileup(path, pil); have > 0)
+		fprintf(stderr, "pileup: %llu sites on the %zu sequences of the reference genome, %llu positions with an aligned column (`colord_hip info --pileup [--min-alt N] [--min-frac F]` prints the sites, `--pileup --vcf` a VCF, `--pileup --summary [--json]` what the table adds up to)\n",
+			(unsigned long long)pil.sites.size(), pil.seq_len.size(), (unsigned long long)pil.sums.covered);
+	else if (have < 0) fprintf(stderr, "pileup: a `hippileup` stream this build cannot read\n");
 	return 0;
 }
 

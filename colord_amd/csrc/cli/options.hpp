@@ -44,6 +44,7 @@ struct Options {
 	bool kmer_spectrum = false;                     // --kmer-spectrum: the count spectrum of the k-mers pass 1 counted (cl_ctx_set_kmer_spectrum) in a `hipkmers` stream
 	bool sketch = false; long sketch_size = -1, sketch_min_count = -1;   // --sketch [--sketch-size N] [--sketch-min-count M]: the MinHash sketch of the k-mers pass 1 counted at least M times (cl_ctx_set_kmer_sketch) in a `hipsketch` stream; defaults 10 000 and 2
 	bool mappings = false;                          // --mappings (with -G): the read-to-genome alignments the edit scripts hold (cl_ctx_set_mappings) in a `hipmappings` stream
+	bool pileup = false; long pileup_min_depth = -1, pileup_min_alt = -1; double pileup_min_frac = -1;   // --pileup (with -G) [--pileup-min-depth N] [--pileup-min-alt N] [--pileup-min-frac F]: the per-position base counts of the reads on the genome's pieces (cl_ctx_set_pileup); their sites in a `hippileup` stream; defaults 4, 3 and 0.25
 	bool overlaps = false;                          // --overlaps: the read-to-read overlaps the edit scripts hold (cl_ctx_set_overlaps) in a `hipoverlaps` stream
 	uint64_t qual_domain_symbols = 0;               // --qual-domain-symbols N: the quality models start afresh about every N symbols (cl_compressor_set_qual_domain_symbols; stream `hipqdomains`)
 	int gpus = 1; std::vector<int> gpu_list; std::string transport = "rccl";   // --gpus N [--gpu-list a,b,..] [--transport rccl|host]: reads sharded over N GPUs (run_compress_multi)
@@ -55,7 +56,7 @@ inline void usage()
 {
 	fprintf(stderr,
 		"usage: colord_hip compress-ont|compress-pbhifi|compress-pbraw [options] input.fastq|fasta[.gz] output.colord\n"
-		"       colord_hip decompress [--ignore-digest] [--gpu N] archive.colord output.fastq\n       colord_hip check [--gpu N] archive.colord\n       colord_hip info [--report [--json]] [--edit-profile [--json]] [--kmer-spectrum [--json]] archive.colord\n       colord_hip info --overlaps [--min-block N] [--names] archive.colord\n       colord_hip info --mappings [--min-block N] [--names] | --mappings --coverage W | --mappings --summary [--json] archive.colord\n       colord_hip info --sketch [--json] archive.colord\n       colord_hip dist [--json] A.colord B.colord [C.colord ...]\n"
+		"       colord_hip decompress [--ignore-digest] [--gpu N] archive.colord output.fastq\n       colord_hip check [--gpu N] archive.colord\n       colord_hip info [--report [--json]] [--edit-profile [--json]] [--kmer-spectrum [--json]] archive.colord\n       colord_hip info --overlaps [--min-block N] [--names] archive.colord\n       colord_hip info --mappings [--min-block N] [--names] | --mappings --coverage W | --mappings --summary [--json] archive.colord\n       colord_hip info --pileup [--min-alt N] [--min-frac F] [--vcf] | --pileup --summary [--json] archive.colord\n       colord_hip info --sketch [--json] archive.colord\n       colord_hip dist [--json] A.colord B.colord [C.colord ...]\n"
 		"options (as the reference, arg_parse.cpp:455-640):\n"
 		"  -p,--priority ratio|balanced|memory   -k,--kmer-len K with -a,--anchor-len A (both or none)\n"
 		"  -q,--qual org|none|avg|2-fix|4-fix|5-fix|2-avg|4-avg|5-avg   -T,--qual-thresholds a,b,..   -D,--qual-values a,b,..\n"
@@ -141,6 +142,16 @@ inline void usage()
 		"                     WHAT IT IS NOT: A READ CODED AGAINST EARLIER READS INSTEAD OF GENOME PIECES YIELDS NO RECORD, AND A READ THAT SPANS A PIECE BOUNDARY YIELDS ONE RECORD PER\n"
 		"                     PIECE; THESE ARE NOT STITCHED.  `decompress` / `check` ignore the stream.  Works with --stream-input, --part-symbols, --chunk-bases and every other view.\n"
 		"                     Not without -G, not with --gpus > 1, --domains > 1 or --overlaps.  Cost: the walk of --overlaps and 48 bytes read and written per record (DESIGN.md 4m, 9)\n"
+		"  --pileup           with -G: per-position base counts of the reads on the genome, made on the device from the edit scripts: for every genome position the read columns that match, that say\n"
+		"                     A, C, G or T instead (in the genome's forward orientation), that delete it, and the insertion RUNS left of which it lies (a run counts once: unaligned read ends are\n"
+		"                     coded as long runs).  THE FULL TABLE IS NOT STORED, it is the size of the genome: the archive gets its totals and its SITES (stream `hippileup`, 48 bytes per site and\n"
+		"                     the genome's sequence names and lengths; the reference's decompressor ignores it) — positions of depth >= --pileup-min-depth N (4) whose strongest alternative has\n"
+		"                     >= --pileup-min-alt N (3) columns and >= --pileup-min-frac F (0.25) of the depth.  The defaults are interface defaults, chosen so that isolated read errors do not\n"
+		"                     qualify at ONT error rates; THEY ARE NOT TUNED AGAINST ANYTHING.  `colord_hip info --pileup [--min-alt N] [--min-frac F] archive` prints the sites as a table (name, 1-based\n"
+		"                     position, ref, depth, A, C, G, T, del, ins, kind; the options can only tighten what was stored), `info --pileup --vcf` the base sites as a minimal VCF 4.2,\n"
+		"                     `info --pileup --summary [--json]` totals, mean depth, rates and sites per kind; none decodes `dna` or `qual` or needs a GPU.  READS CODED AGAINST EARLIER READS INSTEAD OF\n"
+		"                     GENOME PIECES COUNT NOTHING; there are no per-strand counts.  Independent of --mappings (both may be given).  Not without -G, not with --gpus > 1, --domains > 1 or\n"
+		"                     --overlaps.  Cost: one more walk of the tuple bytes per chunk and 36 bytes of device memory per genome position (DESIGN.md 4n, 9)\n"
 		"  --qual-domain-symbols N   model domains of the QUALITY stream alone: its adaptive models start afresh at the first part boundary at which a domain holds N coded\n"
 		"                     symbols, and the starts are recorded (stream `hipqdomains`).  `colord_hip decompress --gpu N` / `check --gpu N` then decode the domains side by\n"
 		"                     side on the device, one lane each; without --gpu they decode on the host as one chain that starts afresh at every domain.  The k-mer set, the\n"
@@ -214,6 +225,10 @@ inline Options parse_options(int argc, char** argv)
 		else if (a == "--sketch-min-count") { O.sketch_min_count = atol(need(i).c_str()); if (O.sketch_min_count < 1 || O.sketch_min_count > 0x7fffffffl) die("--sketch-min-count must be in [1, 2147483647]"); }
 		else if (a == "--overlaps") O.overlaps = true;
 		else if (a == "--mappings") O.mappings = true;
+		else if (a == "--pileup") O.pileup = true;
+		else if (a == "--pileup-min-depth") { O.pileup_min_depth = atol(need(i).c_str()); if (O.pileup_min_depth < 0 || O.pileup_min_depth > 0x7fffffffl) die("--pileup-min-depth must be in [0, 2147483647]"); }
+		else if (a == "--pileup-min-alt") { O.pileup_min_alt = atol(need(i).c_str()); if (O.pileup_min_alt < 0 || O.pileup_min_alt > 0x7fffffffl) die("--pileup-min-alt must be in [0, 2147483647]"); }
+		else if (a == "--pileup-min-frac") { char* e = nullptr; const std::string v = need(i); O.pileup_min_frac = strtod(v.c_str(), &e); if (v.empty() || *e || !(O.pileup_min_frac >= 0 && O.pileup_min_frac <= 1)) die("--pileup-min-frac must be in [0, 1]"); }
 		else if (a == "--parse-threads") { O.parse_threads = atoi(need(i).c_str()); if (O.parse_threads < 1 || O.parse_threads > 256) die("--parse-threads must be in [1, 256]"); }
 		else if (a == "-h" || a == "--help") { usage(); exit(0); }
 		else if (!a.empty() && a[0] == '-' && a.size() > 1) die("unknown option " + a);
@@ -255,6 +270,17 @@ inline Options parse_options(int argc, char** argv)
 		if (O.gpus > 1) die("--mappings is not available with --gpus > 1 (the records of the ranks are not merged yet)");
 		if (O.domains > 1) die("--mappings is not available with --domains > 1 (every domain is a compressor of its own)");
 		if (O.overlaps) die("--mappings is not available with --overlaps (which refuses -G)");
+	}
+	if (!O.pileup && (O.pileup_min_depth >= 0 || O.pileup_min_alt >= 0 || O.pileup_min_frac >= 0)) { usage(); die("--pileup-min-depth, --pileup-min-alt and --pileup-min-frac need --pileup"); }
+	if (O.pileup)
+	{	// a column lies on a piece of the reference genome, placed by ONE geometry in ONE table on ONE device
+		if (O.genome.empty()) die("--pileup needs a reference genome (-G): its columns are alignments against the genome's pieces");
+		if (O.gpus > 1) die("--pileup is not available with --gpus > 1 (the tables of the ranks are not added yet)");
+		if (O.domains > 1) die("--pileup is not available with --domains > 1 (every domain is a compressor of its own)");
+		if (O.overlaps) die("--pileup is not available with --overlaps (which refuses -G)");
+		if (O.pileup_min_depth < 0) O.pileup_min_depth = 4;
+		if (O.pileup_min_alt < 0) O.pileup_min_alt = 3;
+		if (O.pileup_min_frac < 0) O.pileup_min_frac = 0.25;
 	}
 	if (O.overlaps)
 	{	// a record names reads of the input: every reference id must be one of them, in ONE set of reference reads

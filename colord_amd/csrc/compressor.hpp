@@ -72,6 +72,8 @@ struct cl_compressor {
 	DevBuf<uint32_t> ref_read;                      // cl_ctx_set_overlaps: reference id -> index of that read in the input (n_refs_total entries), made in refs_finish
 	DevBuf<uint64_t> map_seq_len; DevBuf<uint32_t> map_piece_first; // cl_compressor_genome_geometry: the tables of the pseudo reads' geometry (mappings.hpp) ...
 	MapGeom map_geom{}; bool has_map_geom = false;  // ... and the geometry over them, for the lifts of cl_ctx_set_mappings
+	std::vector<uint64_t> map_seq_len_h;            // ... and the sequence lengths on the host, for the table of cl_ctx_set_pileup
+	cl_pileup* pileup = nullptr;                    // cl_ctx_set_pileup: the ONE table of this compressor, made in refs_finish; every lane adds into it (pileup.hip)
 	cl_dna_coder* dna = nullptr; cl_qual_coder* qual = nullptr;
 	uint64_t qual_domain_symbols = 0;               // cl_compressor_set_qual_domain_symbols: handed to the quality coder when it is created
 	// pass 2b

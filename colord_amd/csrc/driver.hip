@@ -12,6 +12,7 @@ extern "C" cl_status cl_compress_shard(cl_ctx* ctx, const cl_compress_params* P,
 	if (!ctx || !P || !reads || !h_part_bounds || !h_pack_bounds || !dna || !info) return cl_fail(ctx, CL_E_INVALID, "cl_compress_shard: null argument");
 	if (qual && (!d_quals || !d_base_off || !h_qual_part_sizes)) return cl_fail(ctx, CL_E_INVALID, "cl_compress_shard: quality coder without qualities");
 	if (ctx->mappings) return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_compress_shard: cl_ctx_set_mappings needs the pseudo reads of a reference genome, which one shard does not have (cl_compressor)");
+	if (ctx->pileup) return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_compress_shard: cl_ctx_set_pileup needs the pseudo reads of a reference genome, which one shard does not have (cl_compressor)");
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	memset(info, 0, sizeof(*info));
 	const uint32_t n = reads->n_reads;
@@ -56,7 +57,7 @@ extern "C" cl_status cl_compress_shard(cl_ctx* ctx, const cl_compress_params* P,
 		HIP_TRY(ctx, hipMemsetAsync(ref_read.p, 0xff, (uint64_t)refs.p->n_reads * 4, cl_launch_stream(ctx)));
 		CL_TRY(overlaps_ref_reads(ctx, cl_index_ref_rank(index), n, 0, ref_read.p, refs.p->n_reads));
 	}
-	CL_TRY(tuple_streams(ctx, P, lists, index, refs, reads, cl_index_ref_rank(index), h_pack_bounds, n_packs, 0, ref_read.p, ref_read.p ? refs.p->n_reads : 0u, nullptr, ts));
+	CL_TRY(tuple_streams(ctx, P, lists, index, refs, reads, cl_index_ref_rank(index), h_pack_bounds, n_packs, 0, ref_read.p, ref_read.p ? refs.p->n_reads : 0u, nullptr, nullptr, ts));
 	info->n_anchors = ts.n_anchors; info->tuple_bytes = ts.es_bytes;
 	return coder.code(refs, ts);
 }

@@ -201,6 +201,7 @@ extern "C" cl_status cl_compressor_genome_geometry(cl_compressor* c, const uint6
 			}
 	}
 	c->map_seq_len = std::move(T.seq_len); c->map_piece_first = std::move(T.piece_first); c->map_geom = T.G; c->has_map_geom = true;
+	c->map_seq_len_h.assign(h_seq_len, h_seq_len + n_seqs);
 	return CL_OK;
 }
 extern "C" cl_status cl_compressor_mappings(const cl_compressor* c, cl_overlap* h_out, uint64_t cap, uint64_t* n_out)

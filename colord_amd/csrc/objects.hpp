@@ -81,6 +81,11 @@ cl_status overlaps_records(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_e
 // (geom: mappings.hpp, tables on the device; null is an error) and kept on the host by the context that made them
 struct MapGeom;
 cl_status mappings_chunk(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, const MapGeom* geom);
+// pileup.hip (cl_ctx_set_pileup): a batch of tuple streams added to the compressor's table `p` (null is an error) by a launch on `ctx`, the context that
+// made them; and that table made for a compressor whose references are finished, from the geometry kept for the mappings
+struct cl_compressor;
+cl_status pileup_chunk(cl_ctx* ctx, cl_pileup* p, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads);
+cl_status pileup_for_compressor(cl_compressor* c);
 const cl_qual_params* cl_qual_coder_params(const cl_qual_coder* q);     // qual.hip: the parameters the coder was created with
 
 // the DNA coder's state-independent half ahead of time (dna.hip): lookahead.hip walks the NEXT chunk's tuples from the hook that

@@ -115,7 +115,7 @@ inline cl_status verify_streams(cl_ctx* ctx, const cl_reads* reads, const cl_rea
 }
 inline cl_status tuple_streams(cl_ctx* ctx, const cl_compress_params* P, Handle<cl_kmer_lists, cl_kmer_lists_free>& lists, const cl_index* index, const cl_reads* refs,
                                const cl_reads* reads, const uint32_t* d_bounds, const uint32_t* h_pack_bounds, uint32_t n_packs, uint64_t first_read, const uint32_t* d_ref_read,
-                               uint32_t n_ref_read, const MapGeom* map_geom, TupleStreams& out)
+                               uint32_t n_ref_read, const MapGeom* map_geom, cl_pileup* pileup, TupleStreams& out)
 {
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	const uint32_t n = reads->n_reads;
@@ -152,7 +152,9 @@ inline cl_status tuple_streams(cl_ctx* ctx, const cl_compress_params* P, Handle<
 	// cl_ctx_set_overlaps: the batch's first read is read `first_read` of the input; d_ref_read: reference id -> input index (overlaps.hip)
 	if (ctx->overlaps) CL_TRY(overlaps_chunk(ctx, refs, out.es.p, out.es_off.p, n, first_read, d_ref_read, n_ref_read));
 	// cl_ctx_set_mappings: the same walk with the ids as they are, then the lift to the genome's sequences (mappings.hip)
-	return ctx->mappings ? mappings_chunk(ctx, refs, out.es.p, out.es_off.p, n, first_read, map_geom) : CL_OK;
+	if (ctx->mappings) CL_TRY(mappings_chunk(ctx, refs, out.es.p, out.es_off.p, n, first_read, map_geom));
+	// cl_ctx_set_pileup: the walk once more, every tuple on a genome piece booked at its genome position in the compressor's table (pileup.hip)
+	return ctx->pileup ? pileup_chunk(ctx, pileup, refs, out.es.p, out.es_off.p, n) : CL_OK;
 }
 
 // The coder tail of a batch: a14 + a16 the DNA stream, a13 + a15 the quality stream.  The quality stream of level 1 does not depend on

@@ -44,6 +44,7 @@ cl_compressor::~cl_compressor()
 	la.stop();
 	if (getenv("COLORD_HIP_STREAM_DEBUG")) la.report(enc_chunk);
 	for (auto* r : ref_pieces) cl_reads_free(r);
+	if (pileup) cl_pileup_free(pileup);
 	if (refs) cl_reads_free(refs);
 	if (index) cl_index_free(index);
 	if (kset) cl_kmer_set_free(kset);
@@ -341,10 +342,17 @@ extern "C" cl_status cl_compressor_refs_finish(cl_compressor* c)
 		if (!c->n_pseudo) return cl_fail(ctx, CL_E_INVALID, "cl_ctx_set_mappings: needs the pseudo reads of a reference genome (cl_compressor_pseudo_reads)");
 		if (!c->has_map_geom) return cl_fail(ctx, CL_E_INVALID, "cl_ctx_set_mappings: needs the geometry of the pseudo reads (cl_compressor_genome_geometry)");
 	}
+	if (ctx->pileup)
+	{	// a column lies on a piece of the genome, placed by the geometry: one rank, pseudo reads, and the geometry they were cut by
+		if (c->world > 1) return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_ctx_set_pileup: not with reads sharded over ranks (the tables of the ranks are not added yet)");
+		if (!c->n_pseudo) return cl_fail(ctx, CL_E_INVALID, "cl_ctx_set_pileup: needs the pseudo reads of a reference genome (cl_compressor_pseudo_reads)");
+		if (!c->has_map_geom) return cl_fail(ctx, CL_E_INVALID, "cl_ctx_set_pileup: needs the geometry of the pseudo reads (cl_compressor_genome_geometry)");
+	}
 	uint64_t n_pairs = c->pair_ids.n;
 	if (c->world > 1) CL_TRY(gather_refs(c, pk, iv, ln, words, nr, n_pairs));
 	CL_TRY(cl_reads_from_arena(ctx, pk.p, iv.p, ln.p, nr, &c->refs));
 	pk.release(); iv.release(); ln.release();
+	if (ctx->pileup) CL_TRY(pileup_for_compressor(c));                        // the ONE table: the pieces are reads 0 .. n_pseudo-1 of the arena just made
 	CL_TRY(cl_index_build_pairs(ctx, c->kset, c->pair_ids.buf.p, c->pair_refs.buf.p, n_pairs, nullptr, 0, c->n_refs_total, c->n_pseudo, c->P.cs, &c->index));
 	c->pair_ids.buf.release(); c->pair_refs.buf.release(); c->pair_ids.n = c->pair_refs.n = 0;
 	// the coders of this rank's model domain; cur_read_id starts at the global index of the first read, so that the ids of
@@ -367,7 +375,7 @@ cl_status compressor_tuple_streams(cl_compressor* c, cl_ctx* ctx, size_t idx, co
 	Handle<cl_kmer_lists, cl_kmer_lists_free> lists;            // a4: accepted k-mers per read
 	CL_TRY(cl_accepted_kmers(ctx, c->kset, reads, c->P.k, c->P.f, lists.out()));
 	uint64_t g = c->first_read; for (size_t i = 0; i < idx; ++i) g += c->chunk_reads[i];      // the chunk's first read in the whole input
-	return tuple_streams(ctx, &c->P, lists, c->index, c->refs, reads, c->bounds[idx].p, h_pack_bounds, n_packs, g, c->ref_read.p, c->ref_read.p ? c->n_refs_total : 0u, c->has_map_geom ? &c->map_geom : nullptr, out);
+	return tuple_streams(ctx, &c->P, lists, c->index, c->refs, reads, c->bounds[idx].p, h_pack_bounds, n_packs, g, c->ref_read.p, c->ref_read.p ? c->n_refs_total : 0u, c->has_map_geom ? &c->map_geom : nullptr, c->pileup, out);
 }
 
 extern "C" cl_status cl_compressor_encode(cl_compressor* c, const cl_reads* reads, const uint8_t* d_quals, const uint64_t* d_base_off,

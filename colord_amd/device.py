@@ -60,7 +60,8 @@ class _OrderedLib:
                   "cl_kspec_clear", "cl_kspec_add", "cl_ctx_set_kmer_spectrum", "cl_ctx_kmer_spectrum", "cl_compressor_kmer_spectrum",
                   "cl_sketch_hash", "cl_sketch_create", "cl_sketch_info", "cl_sketch_entries", "cl_sketch_merge", "cl_ctx_set_kmer_sketch", "cl_ctx_kmer_sketch", "cl_compressor_kmer_sketch",
                   "cl_overlaps_host", "cl_ctx_set_overlaps", "cl_ctx_overlaps", "cl_compressor_overlaps",
-                  "cl_mappings_lift_host", "cl_ctx_set_mappings", "cl_ctx_mappings", "cl_compressor_mappings")
+                  "cl_mappings_lift_host", "cl_ctx_set_mappings", "cl_ctx_mappings", "cl_compressor_mappings",
+                  "cl_pileup_host", "cl_pileup_positions", "cl_ctx_set_pileup")
 
     def __init__(self, lib, device):
         self._lib, self._device, self._cache = lib, device, {}
@@ -279,6 +280,18 @@ class Context:
         out = torch.empty((cap, 12), dtype=torch.int32, device=self.device)
         _check(self, self.lib.cl_mappings_lift(*args, out.data_ptr() if cap else None, cap, C.byref(need)))
         return out[:need.value]
+
+    def set_pileup(self, on: bool = True):
+        """cl_ctx_set_pileup: a compressor of this context (one with pseudo reads and their geometry) makes one table of per-position base counts
+        in refs_finish(), and every batch of tuple streams it makes is added to it (Compressor.pileup)."""
+        self.lib.cl_ctx_set_pileup(self.h, int(bool(on)))
+
+    def pileup(self, refs: "Reads", seq_len, read_len: int, overlap: int) -> "Pileup":
+        """cl_pileup_create: the zeroed table for the genome whose pieces are the first reads of the arena refs, which must outlive finish()."""
+        sl = np.ascontiguousarray(np.asarray(seq_len, dtype=np.uint64))
+        h = N._P()
+        _check(self, self.lib.cl_pileup_create(self.h, refs.h, sl.ctypes.data if len(sl) else None, len(sl), read_len, overlap, C.byref(h)))
+        return Pileup(self, h)
 
     def set_kmer_spectrum(self, on: bool = True):
         """cl_ctx_set_kmer_spectrum: every count_filter() on this context, and the pass 1 of its compressors, adds the count spectrum of the
@@ -748,6 +761,61 @@ class _Obj:
         return _view(ptr, n, dtype, self.ctx.device)
 
 
+class Pileup(_Obj):
+    """cl_pileup: per-position base counts of the reads aligned to a reference genome's pieces (csrc/pileup.hip)."""
+    _free = "cl_pileup_free"
+    SITE_FIELDS = ("seq", "pos", "ref", "kind", "match", "subA", "subC", "subG", "subT", "del", "ins", "depth")
+    COLUMNS = ("match", "subA", "subC", "subG", "subT", "del", "ins", "ref")
+
+    def __init__(self, ctx, h, owned=True):
+        super().__init__(ctx, h)
+        self.owned = owned
+
+    def free(self):
+        if self.owned:
+            super().free()
+        self.h = None
+
+    @property
+    def n_pos(self): return self.ctx.lib.cl_pileup_positions(self.h)
+
+    def add(self, refs: "Reads", es: torch.Tensor, es_off: torch.Tensor, max_blocks: int = 0):
+        """cl_pileup_add: the tuple streams es / es_off (n + 1 byte offsets) against the arena the table was created for.  A malformed stream
+        raises (CL_E_INVALID, the text names the first such read) and spoils the table."""
+        es, es_off = es.contiguous(), es_off.contiguous()
+        n = max(es_off.numel() - 1, 0)
+        _check(self.ctx, self.ctx.lib.cl_pileup_add(self.h, refs.h, es.data_ptr() if n else None, es_off.data_ptr() if n else None, n, max_blocks))
+
+    def finish(self):
+        _check(self.ctx, self.ctx.lib.cl_pileup_finish(self.h))
+
+    def columns(self, first: int = 0, n: "int | None" = None) -> np.ndarray:
+        """cl_pileup_columns: (n, 8) uint32 — match, sub A C G T, del, ins, ref — of the positions first .. first + n - 1"""
+        n = self.n_pos - first if n is None else n
+        out = np.zeros((n, 8), np.uint32)
+        _check(self.ctx, self.ctx.lib.cl_pileup_columns(self.h, first, n, out.ctypes.data if n else None))
+        return out
+
+    def sites(self, min_depth: int = 4, min_alt: int = 3, min_permille: int = 250, cap: "int | None" = None) -> np.ndarray:
+        """cl_pileup_sites: (m, 12) uint32 in the field order of cl_pileup_site, in genome order.  With cap the call is made once with room for
+        cap records (CL_E_CAPACITY raises); without, the need is asked for first."""
+        need = C.c_uint64(0)
+        args = (self.h, min_depth, min_alt, min_permille)
+        if cap is None:
+            st = self.ctx.lib.cl_pileup_sites(*args, None, 0, C.byref(need))
+            if st not in (N.CL_OK, N.CL_E_CAPACITY):
+                _check(self.ctx, st)
+            cap = need.value
+        out = np.zeros((cap, 12), np.uint32)
+        _check(self.ctx, self.ctx.lib.cl_pileup_sites(*args, out.ctypes.data if cap else None, cap, C.byref(need)))
+        return out[:need.value]
+
+    def totals(self) -> dict:
+        s = N.PileupSums()
+        _check(self.ctx, self.ctx.lib.cl_pileup_totals(self.h, C.byref(s)))
+        return s.as_dict()
+
+
 class Reads(_Obj):
     _free = "cl_reads_free"
 
@@ -967,6 +1035,12 @@ class Compressor(_Obj):
     def mappings(self) -> np.ndarray:
         """cl_compressor_mappings: the lifted records of the chunks whose tuple streams are made (Context.set_mappings), in input order."""
         return _overlap_records(self.ctx.lib.cl_compressor_mappings, self.h)
+
+    def pileup(self) -> "Pileup":
+        """cl_compressor_pileup: the compressor's table (Context.set_pileup), finished, after the last encode(); it goes with the compressor."""
+        h = N._P()
+        _check(self.ctx, self.ctx.lib.cl_compressor_pileup(self.h, C.byref(h)))
+        return Pileup(self.ctx, h, owned=False)
 
     def prepare(self, reads: "Reads", pack_bounds, part_bounds=None, quals: torch.Tensor | None = None, base_off: torch.Tensor | None = None):
         """cl_compressor_prepare[_parts]: announce a chunk of a later encode() call; its candidates / anchors / edit scripts are

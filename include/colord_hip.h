@@ -630,6 +630,75 @@ cl_status cl_mappings_lift_host(const cl_overlap* h_recs, uint64_t n, const uint
 void cl_ctx_set_mappings(cl_ctx* ctx, int on);
 cl_status cl_ctx_mappings(const cl_ctx* ctx, cl_overlap* h_out, uint64_t cap, uint64_t* n_out);
 
+/* ---- pileup (no counterpart in the reference) — what a reference-genome run aligned, per genome position ------------- */
+/* The second half of what a -G run aligns: which genome position every read base was aligned to, and what the read said there.  The
+ * geometry is that of cl_mappings_lift; the table has n_pos = sum of seq_len[s] positions, sequence s from the sum of the lengths before
+ * it on.  A tuple met on reference id < n_pseudo, taken reversed or not, at cursor c of a piece of len bases that starts at table
+ * position `origin` touches position origin + (rev ? len - 1 - c : c).  Tuples on an id >= n_pseudo (a read) count nothing; the walk, its
+ * cursor and every check go on as in cl_edit_profile.  Per position eight 32-bit counters (cl_pileup_columns), which wrap at 2^32:
+ *   match     match tuples and anchor bases
+ *   sub[4]    subst tuples by the READ's base (A C G T) in the genome's FORWARD orientation (complemented when the piece is taken reversed)
+ *   del       one per deleted reference base
+ *   ins       one per insertion RUN — a maximal row of consecutive ins tuples in the stream; the start tuple, an alt-id and a main-ref
+ *             end a row — booked at the forward position LEFT of it: cursor - 1 taken forward (none at cursor 0 or past the piece's
+ *             end), len - 1 - cursor taken reversed (none at cursor >= len).  A run with no such position is counted in ins_unplaced only.
+ *             (Unaligned read ends are coded as long insertion runs: per base they would bury the channel.)
+ *   ref       the genome's base 0..3, filled by cl_pileup_finish
+ * depth = match + sub + del.  An anchor of L > 0 bases is booked as a difference (+1 at its first position, -1 behind its last, modulo
+ * 2^32) that cl_pileup_finish sums up into `match`.  Pieces overlap in the genome, so two pieces can reach one position; a read column
+ * lies on one piece only, so nothing is counted twice.
+ * WHAT IT IS NOT: reads coded against earlier reads instead of genome pieces count nothing; there are no per-strand counts; the
+ * thresholds' defaults (4 / 3 / 250) are interface defaults, chosen so that isolated read errors do not qualify at ONT error rates, and
+ * are not tuned against anything. */
+typedef struct cl_pileup cl_pileup;
+/* a site: its sequence and 0-based position in it, the genome's base, the channel that won (0..3 a base, 4 del, 5 ins), the counters */
+typedef struct cl_pileup_site { uint32_t seq, pos, ref, kind, match, sub[4], del, ins, depth; } cl_pileup_site;
+/* positions with depth >= 1; the sums of match, sub (all four), del and ins over the table; insertion runs without a position; the reads
+ * of which a tuple (ins, del, match, subst, anchor or skip) was met on a genome piece */
+typedef struct cl_pileup_sums { uint64_t covered, match, sub, del, ins, ins_unplaced, reads; } cl_pileup_sums;
+/* The table for the genome whose pieces are reads 0 .. n_pseudo-1 of the arena `refs` (n_pseudo: the geometry's piece count), allocated
+ * and zeroed: 36 bytes per position.  The piece count and every piece length are checked against the arena as
+ * cl_compressor_genome_geometry checks them (CL_E_INVALID); read_len <= overlap is CL_E_INVALID; a sequence of 2^32 bases or more, 2^32
+ * pieces or more and a table of 2^32 positions or more CL_E_UNSUPPORTED; an allocation that fails CL_E_NOMEM, the text giving the bytes
+ * needed.  `refs` must stay alive and unchanged until cl_pileup_finish has run. */
+cl_status cl_pileup_create(cl_ctx* ctx, const cl_reads* refs, const uint64_t* h_seq_len, uint32_t n_seqs, uint32_t read_len, uint32_t overlap, cl_pileup** out);
+void cl_pileup_free(cl_pileup* p);
+/* n_reads tuple streams (d_es / d_es_off as cl_encode_reads writes them) against `refs` — the arena given to cl_pileup_create, anything
+ * else is CL_E_INVALID — added to the table.  On the device (k_pileup_walk): a wave per read, persistent blocks of four waves (max_blocks
+ * bounds the grid, 0: four per CU; it changes no result), every tuple booked by its own lane with one device atomic, an anchor with two.
+ * Safe from several threads at once on one object: the adds are device atomics on integers, and no result depends on their order.  A
+ * malformed stream (the cases of cl_edit_profile) is CL_E_INVALID, the text naming the first such read; it never makes the kernel read
+ * or write out of range, but the adds of the tuples before it cannot be taken back: the object is SPOILED, and every later call on it
+ * but cl_pileup_free is refused (CL_E_INVALID). */
+cl_status cl_pileup_add(cl_pileup* p, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint32_t max_blocks);
+/* Once, after the last add (adds are refused afterwards, and so is a second finish: CL_E_INVALID): the anchors' running sum goes into
+ * `match`, `ref` is filled from the pieces, the totals are summed (k_pileup_fold). */
+cl_status cl_pileup_finish(cl_pileup* p);
+/* after cl_pileup_finish.  The counters of positions first .. first + n - 1 of the table into h_out, 8 uint32 each: match, sub A C G T,
+ * del, ins, ref (first + n > n_pos: CL_E_INVALID). */
+cl_status cl_pileup_columns(const cl_pileup* p, uint64_t first, uint64_t n, uint32_t* h_out);
+/* The sites in genome order into h_out (host, cap records): positions with depth >= min_depth whose ALT — the largest of sub[b] for
+ * b != ref, del and ins, ties to the lowest kind — is >= min_alt and alt * 1000 >= min_permille * depth (k_pileup_sites: a lane per
+ * position; one pass counts, a prefix sum places, the same kernel body fills).  *n_out = the sites.  cap too small (or h_out null):
+ * CL_E_CAPACITY, *n_out holds the need and nothing was written. */
+cl_status cl_pileup_sites(const cl_pileup* p, uint32_t min_depth, uint32_t min_alt, uint32_t min_permille, cl_pileup_site* h_out, uint64_t cap, uint64_t* n_out);
+cl_status cl_pileup_totals(const cl_pileup* p, cl_pileup_sums* out);
+uint64_t cl_pileup_positions(const cl_pileup* p);                                  /* n_pos */
+/* The whole of it on the HOST (references as in cl_edit_profile_host, the first pieces of the geometry among them), a sequential walk
+ * with the same checks in the same order: h_cols (n_pos x 8 uint32, or null), the sites (h_sites may be null to ask for the count;
+ * CL_E_CAPACITY as above, h_cols and sums are written then too), sums.  bad_read / bad_code (optional): the first malformed read and its
+ * code (cl_edit_profile_error); nothing is written then. */
+cl_status cl_pileup_host(const uint8_t* h_ref_codes, const uint64_t* h_ref_off, uint32_t n_refs, const uint64_t* h_seq_len, uint32_t n_seqs, uint32_t read_len, uint32_t overlap,
+                         const uint8_t* h_es, const uint64_t* h_es_off, uint64_t n_reads, uint32_t min_depth, uint32_t min_alt, uint32_t min_permille,
+                         uint32_t* h_cols, cl_pileup_site* h_sites, uint64_t cap, uint64_t* n_sites, cl_pileup_sums* sums, uint64_t* bad_read, uint32_t* bad_code);
+/* Opt-in (off by default: one flag test per batch, no launch, no allocation, every output byte the same).  While it is on, a compressor
+ * created on this context makes ONE table in cl_compressor_refs_finish, from the geometry of cl_compressor_genome_geometry, and every
+ * batch of tuple streams made by cl_compressor_encode or by one of its encode lanes is added to it.  cl_compressor_refs_finish refuses a
+ * compressor without pseudo reads or without their geometry (CL_E_INVALID) and one that shares its reads with other ranks
+ * (CL_E_UNSUPPORTED); cl_compress_shard has no pseudo reads and refuses the flag (CL_E_UNSUPPORTED).  Every model domain of the command
+ * line is a compressor of its own, with a table of its own: the command line refuses --domains > 1.  Independent of the flags above. */
+void cl_ctx_set_pileup(cl_ctx* ctx, int on);
+
 /* ---- a14 + a16: CDNACoder / CEntrComprReads (dna_coder.{h,cpp}, entr_read.h:56-80) --------------------- */
 typedef struct cl_dna_coder cl_dna_coder;
 /* CDNACoder::Init(true, maxCandidates, level, ., n_ref_genome_pseudo_reads): one adaptive model set that
@@ -806,6 +875,9 @@ cl_status cl_compressor_overlaps(const cl_compressor* c, cl_overlap* h_out, uint
 cl_status cl_compressor_genome_geometry(cl_compressor* c, const uint64_t* h_seq_len, uint32_t n_seqs, uint32_t read_len, uint32_t overlap);
 /* cl_ctx_mappings of the compressor's context (cl_ctx_set_mappings): after the last cl_compressor_encode, of every chunk */
 cl_status cl_compressor_mappings(const cl_compressor* c, cl_overlap* h_out, uint64_t cap, uint64_t* n_out);
+/* The compressor's table (cl_ctx_set_pileup), finished, after the last cl_compressor_encode: *out belongs to the compressor and goes
+ * with it.  CL_E_INVALID: the flag was off when the references were finished, or chunks are still to be coded. */
+cl_status cl_compressor_pileup(cl_compressor* c, cl_pileup** out);
 
 /* cl_qual_coder_set_domain_symbols / cl_qual_coder_domains of the compressor's quality coder.  The setting must be made before the
  * first cl_compressor_encode or cl_compressor_prepare_parts call (CL_E_INVALID afterwards, and without a quality stream); the `dna`
