@@ -208,6 +208,7 @@ int run_compress(int argc, char** argv)
 	if (O.sketch) ck(ctx, cl_ctx_set_kmer_sketch(ctx, 1, (uint32_t)O.sketch_size, (uint32_t)O.sketch_min_count), "cl_ctx_set_kmer_sketch");
 	if (O.overlaps) cl_ctx_set_overlaps(ctx, 1);
 	if (O.mappings) cl_ctx_set_mappings(ctx, 1);
+	if (O.cigars) ck(ctx, cl_ctx_set_cigars(ctx, 1), "cl_ctx_set_cigars");
 	if (O.pileup) cl_ctx_set_pileup(ctx, 1);
 	std::vector<uint64_t> report_lens;                         // --report: every read length, as the reader hands the reads over in pass 1 (N50 / N90)
 	ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, nullptr, estimated_bases(R), &cmp), "cl_compressor_create");
@@ -387,6 +388,12 @@ int run_compress(int argc, char** argv)
 		if (nv) ck(ctx, cl_compressor_mappings(cmp, V.recs.data(), nv, &nv), "cl_compressor_mappings");
 		add_mappings(ar, V, GM, O.genome, n);
 		if (O.verbose) fprintf(stderr, "# mappings: %llu records on %zu sequences\n", (unsigned long long)nv, V.seq_len.size());
+		if (O.cigars)
+		{
+			CigarSet G;
+			add_cigars(ar, ctx, cmp, V, G);
+			if (O.verbose) fprintf(stderr, "# cigars: %zu operations of %zu records, %zu bytes\n", G.ops.size(), G.rec_ops.size(), CigarSet::HEAD + 4 * (G.ops.size() + G.rec_ops.size()));
+		}
 	}
 	if (O.pileup)
 	{

@@ -11,6 +11,7 @@
 #include "edits_stream.hpp"
 #include "overlaps_stream.hpp"
 #include "mappings_stream.hpp"
+#include "cigars_stream.hpp"
 #include "pileup_stream.hpp"
 #include "kspec_stream.hpp"
 #include "sketch_stream.hpp"
@@ -375,6 +376,20 @@ inline void add_mappings(ArchiveWriter& ar, MappingSet& S, const GenomeMode& GM,
 	for (const cl_overlap& o : S.recs) if (o.q >= n_reads || o.t >= S.seq_len.size() || o.te > S.seq_len[o.t] || !(o.flags & OV_GENOME)) die("internal: a mapping record names a read outside the input or lies outside its sequence");
 	const std::vector<uint8_t> b = S.pack();
 	ar.add(ar.reg("hipmappings"), b.data(), b.size(), 0);
+}
+// --cigars: the `hipcigars` stream (cigars_stream.hpp), before finish_archive: the CIGARs the compressor's context and its lanes kept, in the order
+// of the mapping records S; what is written is what the reader will accept
+inline void add_cigars(ArchiveWriter& ar, cl_ctx* ctx, cl_compressor* cmp, const MappingSet& S, CigarSet& G)
+{
+	uint64_t nr = 0, no = 0;
+	const cl_status s = cl_compressor_cigars(cmp, nullptr, 0, &nr, nullptr, 0, &no);
+	if (s != CL_OK && s != CL_E_CAPACITY) ck(ctx, s, "cl_compressor_cigars");
+	G.rec_ops.resize(nr); G.ops.resize(no);
+	if (nr) ck(ctx, cl_compressor_cigars(cmp, G.rec_ops.data(), nr, &nr, G.ops.data(), no, &no), "cl_compressor_cigars");
+	const std::vector<uint8_t> b = G.pack();
+	CigarSet back;
+	if (!back.unpack(b, S)) die("internal: the CIGARs do not fit the mapping records");
+	ar.add(ar.reg("hipcigars"), b.data(), b.size(), 0);
 }
 // --pileup: the `hippileup` stream (pileup_stream.hpp), before finish_archive: the geometry, the thresholds, the totals of the compressor's table, the genome's
 // sequence names and lengths, and the table's sites — the table itself is the size of the genome and stays on the device

@@ -7,6 +7,7 @@
 #include "edits_stream.hpp"
 #include "overlaps_stream.hpp"
 #include "mappings_stream.hpp"
+#include "cigars_stream.hpp"
 #include "pileup_stream.hpp"
 #include "kspec_stream.hpp"
 #include "sketch_stream.hpp"
@@ -116,6 +117,7 @@ int run_info(int argc, char** argv)
 	bool want_report = false, want_edits = false, want_kspec = false, want_sketch = false, want_overlaps = false, names = false, json = false; std::vector<std::string> pos;
 	uint64_t min_block = 0; bool has_min_block = false;
 	bool want_mappings = false, summary = false; uint64_t coverage = 0;          // --mappings [--coverage W | --summary [--json]]
+	bool want_cigar = false, want_sam = false;                                  // --mappings --cigar | --mappings --sam: the PAF with cg:Z:, SAM (`hipcigars`)
 	bool want_pileup = false, vcf = false, has_min_alt = false, has_min_frac = false; uint64_t min_alt = 0; double min_frac = 0;      // --pileup [--min-alt N] [--min-frac F] [--vcf] | --pileup --summary [--json]
 	for (int i = 2; i < argc; ++i)
 	{
@@ -138,6 +140,8 @@ int run_info(int argc, char** argv)
 			if (*end || !(min_frac >= 0 && min_frac <= 1)) die("option --min-frac needs a fraction in [0, 1]");
 		}
 		else if (a == "--mappings") want_mappings = true;
+		else if (a == "--cigar") want_cigar = true;
+		else if (a == "--sam") want_sam = true;
 		else if (a == "--summary") summary = true;
 		else if (a == "--coverage")
 		{
@@ -160,10 +164,11 @@ int run_info(int argc, char** argv)
 	const bool map_paf = want_mappings && !coverage && !summary;            // the three forms of --mappings: PAF (with --min-block, --names), --coverage W, --summary [--json]
 	if (pos.size() != 1 || (json && !wanted && !((want_mappings || want_pileup) && summary)) || wanted + (want_overlaps ? 1 : 0) + (want_mappings ? 1 : 0) + (want_pileup ? 1 : 0) > 1 ||
 	    ((names || has_min_block) && !want_overlaps && !map_paf) || (coverage && !want_mappings) || (summary && !want_mappings && !want_pileup) || (coverage && summary) ||
-	    ((vcf || has_min_alt || has_min_frac) && (!want_pileup || summary)))
+	    ((vcf || has_min_alt || has_min_frac) && (!want_pileup || summary)) || ((want_cigar || want_sam) && (!map_paf || (want_cigar && want_sam))))
 	{
 		fprintf(stderr, "usage: colord_hip info [--report [--json]] [--edit-profile [--json]] [--kmer-spectrum [--json]] archive.colord\n       colord_hip info --overlaps [--min-block N] [--names] archive.colord\n"
 			"       colord_hip info --mappings [--min-block N] [--names] | --mappings --coverage W | --mappings --summary [--json] archive.colord\n"
+			"       colord_hip info --mappings --cigar | --mappings --sam [--min-block N] [--names] archive.colord\n"
 			"       colord_hip info --pileup [--min-alt N] [--min-frac F] [--vcf] | --pileup --summary [--json] archive.colord\n       colord_hip info --sketch [--json] archive.colord\n");
 		return 1;
 	}
@@ -238,6 +243,14 @@ int run_info(int argc, char** argv)
 				ids.push_back(id.empty() ? std::to_string(i) : id);
 			}
 		}
+		if (want_cigar || want_sam)
+		{	// the CIGARs of the records, held against them by the reader
+			CigarSet G; const int hc = read_hipcigars(path, V, G);
+			if (hc == 0) die("no CIGARs are stored in this archive (written without --mappings --cigars)");
+			if (hc < 0) die("the archive's `hipcigars` stream is not one this build reads, or does not fit its `hipmappings` stream");
+			if (!(want_sam ? print_mappings_sam : print_mappings_paf_cigar)(stdout, V, G, min_block, names ? &ids : nullptr)) die("the archive's `hipmappings` stream names a read the `header` stream does not hold");
+			return 0;
+		}
 		if (!print_mappings_paf(stdout, V, min_block, names ? &ids : nullptr)) die("the archive's `hipmappings` stream names a read the `header` stream does not hold");
 		return 0;
 	}
@@ -308,6 +321,10 @@ int run_info(int argc, char** argv)
 		fprintf(stderr, "mappings: %llu records of reads against the %zu sequences of the reference genome (`colord_hip info --mappings [--min-block N] [--names]` prints them as PAF, `--mappings --coverage W` a coverage track, `--mappings --summary [--json]` what they add up to)\n",
 			(unsigned long long)mps.recs.size(), mps.seq_len.size());
 	else if (have < 0) fprintf(stderr, "mappings: a `hipmappings` stream this build cannot read\n");
+	uint64_t cg_records = 0, cg_operations = 0;
+	if (const int have = peek_hipcigars(path, cg_records, cg_operations); have > 0)
+		fprintf(stderr, "cigars: %llu operations of %llu mapping records (`colord_hip info --mappings --cigar` prints the PAF with cg:Z:, `--mappings --sam` SAM)\n", (unsigned long long)cg_operations, (unsigned long long)cg_records);
+	else if (have < 0) fprintf(stderr, "cigars: a `hipcigars` stream this build cannot read\n");
 	PileupSet pil;
 	if (const int have = read_hippileup(path, pil); have > 0)
 		fprintf(stderr, "pileup: %llu sites on the %zu sequences of the reference genome, %llu positions with an aligned column (`colord_hip info --pileup [--min-alt N] [--min-frac F]` prints the sites, `--pileup --vcf` a VCF, `--pileup --summary [--json]` what the table adds up to)\n",

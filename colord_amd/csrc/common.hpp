@@ -365,6 +365,10 @@ struct cl_ctx {
 	bool mappings = false;                       // cl_ctx_set_mappings: tuple_streams (pass_steps.hpp) keeps the lifted records of every batch on genome pieces (mappings.hip)
 	std::map<uint64_t, std::vector<cl_overlap>> mapping_recs;   // ... by the batch's first read (under mappings_mu: cl_ctx_mappings merges the encode lanes')
 	mutable std::mutex mappings_mu;
+	bool cigars = false;                         // cl_ctx_set_cigars (with mappings): the mappings hook keeps the CIGAR of every lifted record too (cigars.hip)
+	struct CigarBatch { std::vector<uint32_t> rec_ops, ops; };   // a count per lifted record of a batch, and the operations one behind the other
+	std::map<uint64_t, CigarBatch> cigar_recs;   // ... by the batch's first read (under cigars_mu: cl_ctx_cigars merges the encode lanes')
+	mutable std::mutex cigars_mu;
 	bool pileup = false;                         // cl_ctx_set_pileup: tuple_streams (pass_steps.hpp) adds every batch on genome pieces to the compressor's table (pileup.hip)
 	uint64_t gap_paths[11] = { 0 };              // cl_ctx_gap_paths: the last cl_encode_reads' gaps per size class 0..7, quad -> wave, giant -> wave, wave-pool redo rounds (owner thread only)
 	std::map<std::string, KernelTime> times;     // per-kernel accumulated HIP-event time of the last API call

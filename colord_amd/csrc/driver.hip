@@ -12,6 +12,7 @@ extern "C" cl_status cl_compress_shard(cl_ctx* ctx, const cl_compress_params* P,
 	if (!ctx || !P || !reads || !h_part_bounds || !h_pack_bounds || !dna || !info) return cl_fail(ctx, CL_E_INVALID, "cl_compress_shard: null argument");
 	if (qual && (!d_quals || !d_base_off || !h_qual_part_sizes)) return cl_fail(ctx, CL_E_INVALID, "cl_compress_shard: quality coder without qualities");
 	if (ctx->mappings) return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_compress_shard: cl_ctx_set_mappings needs the pseudo reads of a reference genome, which one shard does not have (cl_compressor)");
+	if (ctx->cigars) return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_compress_shard: cl_ctx_set_cigars needs the mapping records of a reference genome, which one shard does not have (cl_compressor)");
 	if (ctx->pileup) return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_compress_shard: cl_ctx_set_pileup needs the pseudo reads of a reference genome, which one shard does not have (cl_compressor)");
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	memset(info, 0, sizeof(*info));

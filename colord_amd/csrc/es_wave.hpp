@@ -1,5 +1,5 @@
-// es_wave.hpp — the tuple stream of one read walked by one wave: what k_es_expand (expand.hip), k_edit_profile (edits.hip) and
-// k_overlap_walk (overlaps.hip) share.  The format, the codes and the order of the checks are es_codes.hpp's, as the host walk has them.
+// es_wave.hpp — the tuple stream of one read walked by one wave: what k_es_expand (expand.hip), k_edit_profile (edits.hip),
+// k_overlap_walk (overlaps.hip), k_pileup_walk (pileup.hip) and k_cigar_walk (cigars.hip) share.  The format, the codes and the order of the checks are es_codes.hpp's, as the host walk has them.
 //
 // The wave takes the stream 64 bytes at a time, one byte per lane.  Per window (es_window):
 //   1. tuple starts: a tuple is 1, 4 or 5 bytes long by its type nibble, and payload bytes look like anything, so the starts are a chain

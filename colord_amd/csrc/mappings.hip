@@ -162,9 +162,11 @@ extern "C" cl_status cl_ctx_mappings(const cl_ctx* c, cl_overlap* h_out, uint64_
 cl_status mappings_chunk(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, const MapGeom* geom)
 {
 	if (!geom) return cl_fail(ctx, CL_E_INVALID, "cl_ctx_set_mappings: no genome geometry (cl_compressor_genome_geometry)");
-	uint64_t n_ov = 0, n = 0; DevBuf<cl_overlap> ov, out;
-	CL_TRY(overlaps_records(ctx, refs, d_es, d_es_off, n_reads, first_read, ov, &n_ov));
+	uint64_t n_ov = 0, n = 0; DevBuf<cl_overlap> ov, out; DevBuf<uint64_t> rec_off;
+	CL_TRY(overlaps_records(ctx, refs, d_es, d_es_off, n_reads, first_read, ov, &n_ov, ctx->cigars ? &rec_off : nullptr));
 	CL_TRY(map_run(ctx, *geom, ov.p, n_ov, nullptr, 0, &out, &n));
+	// cl_ctx_set_cigars: the third walk, with the record offsets of this batch's; the records on a piece (id < n_pseudo) are those the lift kept
+	if (ctx->cigars) CL_TRY(cigars_chunk(ctx, refs, d_es, d_es_off, n_reads, first_read, geom->n_pseudo, rec_off.p, n_ov, n));
 	std::vector<cl_overlap> h(n);
 	if (n)
 	{

@@ -75,8 +75,17 @@ cl_status kmer_sketch_range(cl_ctx* ctx, const uint64_t* d_keys, const uint32_t*
 cl_status overlaps_chunk(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, const uint32_t* d_ref_read, uint32_t n_ref_read);
 // ... and that table's entries of one chunk: read i (input index first_read + i) is reference d_bounds[i] iff d_bounds[i + 1] > d_bounds[i] (n + 1 bounds)
 cl_status overlaps_ref_reads(cl_ctx* ctx, const uint32_t* d_bounds, uint32_t n, uint32_t first_read, uint32_t* d_ref_read, uint32_t n_ref_read);
-// ... and the records alone, ids untranslated, in a buffer made by the call (mappings.hip lifts them)
-cl_status overlaps_records(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, DevBuf<cl_overlap>& out, uint64_t* n_out);
+// ... and the records alone, ids untranslated, in a buffer made by the call (mappings.hip lifts them); rec_off (or null) takes the records'
+// offsets per read, n_reads + 1 entries; overlaps_offsets: those offsets alone (the count and the prefix sum, no fill; n_reads > 0)
+cl_status overlaps_records(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, DevBuf<cl_overlap>& out, uint64_t* n_out,
+                           DevBuf<uint64_t>* rec_off = nullptr);
+cl_status overlaps_offsets(cl_ctx* ctx, const char* who, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint32_t max_blocks, DevBuf<uint64_t>& rec_off,
+                           uint64_t* n_out);
+// cigars.hip (cl_ctx_set_cigars, from mappings_chunk): the CIGARs of a batch's records on reference ids below id_limit — the genome's pieces,
+// the records the lift keeps, in their order — copied to the host and kept by the context that made them; d_rec_off / n_rec: that batch's
+// record offsets per read and record count (overlaps_records); n_lifted: the records the lift kept
+cl_status cigars_chunk(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, uint32_t id_limit, const uint64_t* d_rec_off,
+                       uint64_t n_rec, uint64_t n_lifted);
 // mappings.hip (cl_ctx_set_mappings): the records of a batch whose target is a piece of the reference genome, lifted to the genome's sequences
 // (geom: mappings.hpp, tables on the device; null is an error) and kept on the host by the context that made them
 struct MapGeom;

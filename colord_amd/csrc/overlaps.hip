@@ -173,21 +173,14 @@ __global__ __launch_bounds__(256) void k_ref_read_scatter(const uint32_t* __rest
 }
 } // namespace
 
-// count, place, fill.  The records go to d_out (cap records), or — with `own` — to a buffer made here once the count is known.
-static cl_status ov_run(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, const uint32_t* d_ref_read,
-                        uint32_t n_ref_read, uint32_t max_blocks, cl_overlap* d_out, uint64_t cap, DevBuf<cl_overlap>* own, uint64_t* n_out)
+// the count: n_rec[r] and qlen[r] of every read, and off = the prefix sum of n_rec (n_reads + 1 entries), *total = off[n_reads].  `who` names
+// the entry in the text of a refusal.
+static cl_status ov_count(cl_ctx* ctx, const char* who, const OvRefs& R, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, uint32_t grid,
+                          DevBuf<uint32_t>& n_rec, DevBuf<uint32_t>& qlen, DevBuf<uint64_t>& off, uint64_t* total)
 {
-	if (n_out) *n_out = 0;
-	if (!ctx || !refs || !n_out || (n_reads && (!d_es || !d_es_off)) || (n_ref_read && !d_ref_read)) return cl_fail(ctx, CL_E_INVALID, "cl_overlaps_of: null argument");
-	if (first_read + n_reads > OV_POS_MAX + 1) return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_overlaps_of: read indices past 2^32 - 1");
-	if (!n_reads) return CL_OK;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	if (!max_blocks) max_blocks = 4 * (uint32_t)std::max(1, ctx->n_cu);
-	const uint32_t grid = std::min(grid_for(n_reads, 4), max_blocks);
-	DevBuf<uint32_t> n_rec, qlen; DevBuf<uint64_t> off; DevBuf<unsigned long long> g;
+	DevBuf<unsigned long long> g;
 	DEV_ALLOC(ctx, n_rec, n_reads); DEV_ALLOC(ctx, qlen, n_reads); DEV_ALLOC(ctx, off, (uint64_t)n_reads + 1); DEV_ALLOC(ctx, g, 1);
 	HIP_TRY(ctx, hipMemsetAsync(g.p, 0, 8, cl_launch_stream(ctx)));
-	const OvRefs R{ Arena{ nullptr, nullptr, nullptr, refs->lens.p, d_ref_read ? std::min(refs->n_reads, n_ref_read) : refs->n_reads }, d_ref_read };
 	LAUNCH(ctx, k_overlap_walk<false>, grid, 256, R, d_es, d_es_off, n_reads, (uint32_t)first_read, n_rec.p, qlen.p, (const uint64_t*)nullptr, (cl_overlap*)nullptr, g.p);
 	HIP_TRY(ctx, hipGetLastError());
 	unsigned long long h_err = 0;
@@ -197,10 +190,27 @@ static cl_status ov_run(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, 
 	{
 		cl_timing_collect(ctx);
 		const uint64_t key = ~(uint64_t)h_err;
-		return cl_fail(ctx, CL_E_INVALID, "cl_overlaps_of: malformed tuple stream, first: read " + std::to_string(key >> 32) + ": " + ed_error_text((uint32_t)key));
+		return cl_fail(ctx, CL_E_INVALID, std::string(who) + ": malformed tuple stream, first: read " + std::to_string(key >> 32) + ": " + ed_error_text((uint32_t)key));
 	}
+	return cl_scan_u32_u64(ctx, n_rec.p, off.p, n_reads, total);
+}
+
+// count, place, fill.  The records go to d_out (cap records), or — with `own` — to a buffer made here once the count is known.  off_out (or
+// null) takes the records' offsets per read, n_reads + 1 entries.
+static cl_status ov_run(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, const uint32_t* d_ref_read,
+                        uint32_t n_ref_read, uint32_t max_blocks, cl_overlap* d_out, uint64_t cap, DevBuf<cl_overlap>* own, uint64_t* n_out, DevBuf<uint64_t>* off_out = nullptr)
+{
+	if (n_out) *n_out = 0;
+	if (!ctx || !refs || !n_out || (n_reads && (!d_es || !d_es_off)) || (n_ref_read && !d_ref_read)) return cl_fail(ctx, CL_E_INVALID, "cl_overlaps_of: null argument");
+	if (first_read + n_reads > OV_POS_MAX + 1) return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_overlaps_of: read indices past 2^32 - 1");
+	if (!n_reads) return CL_OK;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (!max_blocks) max_blocks = 4 * (uint32_t)std::max(1, ctx->n_cu);
+	const uint32_t grid = std::min(grid_for(n_reads, 4), max_blocks);
+	DevBuf<uint32_t> n_rec, qlen; DevBuf<uint64_t> off;
+	const OvRefs R{ Arena{ nullptr, nullptr, nullptr, refs->lens.p, d_ref_read ? std::min(refs->n_reads, n_ref_read) : refs->n_reads }, d_ref_read };
 	uint64_t total = 0;
-	CL_TRY(cl_scan_u32_u64(ctx, n_rec.p, off.p, n_reads, &total));
+	CL_TRY(ov_count(ctx, "cl_overlaps_of", R, d_es, d_es_off, n_reads, first_read, grid, n_rec, qlen, off, &total));
 	*n_out = total;
 	if (own) { if (total) DEV_ALLOC(ctx, *own, total); d_out = own->p; cap = total; }
 	if (total > cap || (total && !d_out)) { cl_timing_collect(ctx); return cl_fail(ctx, CL_E_CAPACITY, "cl_overlaps_of: need " + std::to_string(total) + " records"); }
@@ -211,6 +221,7 @@ static cl_status ov_run(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, 
 		HIP_TRY(ctx, hipStreamSynchronize(cl_launch_stream(ctx)));
 	}
 	cl_timing_collect(ctx);
+	if (off_out) *off_out = std::move(off);
 	return CL_OK;
 }
 extern "C" cl_status cl_overlaps_of(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read,
@@ -277,10 +288,22 @@ cl_status overlaps_chunk(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es,
 	ctx->overlap_recs[first_read] = std::move(h);
 	return CL_OK;
 }
-// Internal (mappings.hip): the records of one batch with no translation table (`t` is the stream's reference id), in a buffer made here
-cl_status overlaps_records(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, DevBuf<cl_overlap>& out, uint64_t* n_out)
+// Internal (mappings.hip): the records of one batch with no translation table (`t` is the stream's reference id), in a buffer made here;
+// rec_off (or null) takes the records' offsets per read (n_reads + 1 entries), for the walk of cigars.hip
+cl_status overlaps_records(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, DevBuf<cl_overlap>& out, uint64_t* n_out,
+                           DevBuf<uint64_t>* rec_off)
 {
-	return ov_run(ctx, refs, d_es, d_es_off, n_reads, first_read, nullptr, 0, 0, nullptr, 0, &out, n_out);
+	return ov_run(ctx, refs, d_es, d_es_off, n_reads, first_read, nullptr, 0, 0, nullptr, 0, &out, n_out, rec_off);
+}
+// Internal (cigars.hip): those offsets alone, *n_out = the records: the count of k_overlap_walk and the prefix sum, no fill.  n_reads > 0.
+cl_status overlaps_offsets(cl_ctx* ctx, const char* who, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint32_t max_blocks, DevBuf<uint64_t>& rec_off,
+                           uint64_t* n_out)
+{
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (!max_blocks) max_blocks = 4 * (uint32_t)std::max(1, ctx->n_cu);
+	DevBuf<uint32_t> n_rec, qlen;
+	const OvRefs R{ Arena{ nullptr, nullptr, nullptr, refs->lens.p, refs->n_reads }, nullptr };
+	return ov_count(ctx, who, R, d_es, d_es_off, n_reads, 0, std::min(grid_for(n_reads, 4), max_blocks), n_rec, qlen, rec_off, n_out);
 }
 // Internal (stream.hip, driver.hip): the reference id -> read index table of one chunk's `bounds` (n + 1 entries) scattered into d_ref_read
 cl_status overlaps_ref_reads(cl_ctx* ctx, const uint32_t* d_bounds, uint32_t n, uint32_t first_read, uint32_t* d_ref_read, uint32_t n_ref_read)

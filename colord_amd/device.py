@@ -61,6 +61,7 @@ class _OrderedLib:
                   "cl_sketch_hash", "cl_sketch_create", "cl_sketch_info", "cl_sketch_entries", "cl_sketch_merge", "cl_ctx_set_kmer_sketch", "cl_ctx_kmer_sketch", "cl_compressor_kmer_sketch",
                   "cl_overlaps_host", "cl_ctx_set_overlaps", "cl_ctx_overlaps", "cl_compressor_overlaps",
                   "cl_mappings_lift_host", "cl_ctx_set_mappings", "cl_ctx_mappings", "cl_compressor_mappings",
+                  "cl_cigars_host", "cl_cigars_error", "cl_ctx_set_cigars", "cl_ctx_cigars", "cl_compressor_cigars",
                   "cl_pileup_host", "cl_pileup_positions", "cl_ctx_set_pileup")
 
     def __init__(self, lib, device):
@@ -252,6 +253,34 @@ class Context:
         out = torch.empty((cap, 12), dtype=torch.int32, device=self.device)
         _check(self, self.lib.cl_overlaps_of(*args, out.data_ptr() if cap else None, cap, C.byref(need)))
         return out[:need.value]
+
+    def cigars_of(self, refs: "Reads", es: torch.Tensor, es_off: torch.Tensor, id_limit: int = 0, max_blocks: int = 0, caps: "tuple | None" = None):
+        """cl_cigars_of: the CIGARs of the records of cl_overlaps_of over the same streams: (the operation count per record, the operations
+        len << 4 | op of the records one behind the other), two int32 tensors on the device (the bits of uint32).  id_limit: a record on a
+        reference id at or past it gets the count 0 (0: every reference).  With caps = (records, operations) the call is made once with that
+        room (CL_E_CAPACITY raises); without, the needs are asked for first.  A malformed stream raises as in overlaps_of."""
+        es, es_off = es.contiguous(), es_off.contiguous()
+        n = max(es_off.numel() - 1, 0)
+        args = (self.h, refs.h, es.data_ptr() if es.numel() else None, es_off.data_ptr() if n else None, n, id_limit, max_blocks)
+        nr, no = C.c_uint64(0), C.c_uint64(0)
+        if caps is None:
+            st = self.lib.cl_cigars_of(*args, None, 0, C.byref(nr), None, 0, C.byref(no))
+            if st not in (N.CL_OK, N.CL_E_CAPACITY):
+                _check(self, st)
+            caps = (nr.value, no.value)
+        rec = torch.empty(caps[0], dtype=torch.int32, device=self.device)
+        ops = torch.empty(caps[1], dtype=torch.int32, device=self.device)
+        _check(self, self.lib.cl_cigars_of(*args, rec.data_ptr() if caps[0] else None, caps[0], C.byref(nr), ops.data_ptr() if caps[1] else None, caps[1], C.byref(no)))
+        return rec[:nr.value], ops[:no.value]
+
+    def set_cigars(self, on: bool = True):
+        """cl_ctx_set_cigars: on top of set_mappings, every batch leaves the CIGARs of its lifted records too (dropped when switched on);
+        refused without set_mappings."""
+        _check(self, self.lib.cl_ctx_set_cigars(self.h, int(bool(on))))
+
+    def cigars(self):
+        """cl_ctx_cigars: (a count per record of mappings(), the operations one behind the other), two uint32 arrays."""
+        return _cigar_records(self.lib.cl_ctx_cigars, self.h)
 
     def set_mappings(self, on: bool = True):
         """cl_ctx_set_mappings: every batch of tuple streams made by a compressor of this context (one with pseudo reads and their geometry)
@@ -943,9 +972,25 @@ def _overlap_records(fn, h) -> np.ndarray:
     return out[:n.value]
 
 
+def _cigar_records(fn, h):
+    """the CIGARs a context or a compressor keeps (cl_ctx_cigars / cl_compressor_cigars): the needs first, then that many"""
+    nr, no = C.c_uint64(0), C.c_uint64(0)
+    st = fn(h, None, 0, C.byref(nr), None, 0, C.byref(no))
+    if st not in (N.CL_OK, N.CL_E_CAPACITY):
+        _check(None, st)
+    rec, ops = np.zeros(nr.value, np.uint32), np.zeros(no.value, np.uint32)
+    if nr.value:
+        _check(None, fn(h, rec.ctypes.data, nr.value, C.byref(nr), ops.ctypes.data if no.value else None, no.value, C.byref(no)))
+    return rec[:nr.value], ops[:no.value]
+
+
 class Compressor(_Obj):
     """cl_compressor: pass 1 / reference listing / pass 2 over the chunks of an input (csrc/stream.hip)."""
     _free = "cl_compressor_free"
+
+    def cigars(self):
+        """cl_compressor_cigars: the CIGARs of the records of mappings() (Context.set_cigars), in their order."""
+        return _cigar_records(self.ctx.lib.cl_compressor_cigars, self.h)
 
     def overlaps(self) -> np.ndarray:
         """cl_compressor_overlaps: the overlap records of the chunks whose tuple streams are made (Context.set_overlaps), in input order."""

@@ -630,6 +630,41 @@ cl_status cl_mappings_lift_host(const cl_overlap* h_recs, uint64_t n, const uint
 void cl_ctx_set_mappings(cl_ctx* ctx, int on);
 cl_status cl_ctx_mappings(const cl_ctx* ctx, cl_overlap* h_out, uint64_t cap, uint64_t* n_out);
 
+/* ---- CIGARs (no counterpart in the reference) — the alignment of every overlap record, base by base ------------------- */
+/* The CIGAR of a record (a VISIT of cl_overlaps_of that holds an aligned column) is the sequence of the operations of the visit's tuples
+ * in stream order — ins: I 1; del: D 1; match: = 1; subst: X 1; anchor v: = v; skip v: D v (nothing for v = 0) — from the visit's first
+ * aligned column to its last, both included: what lies in front of the first (the entry skip behind an alt-id too) and behind the last is
+ * dropped, the trimming that qs / qe / ts / te do.  Neighbouring equal operations merge; a zero-length anchor or skip between them does
+ * not keep them apart.  An operation is one uint32_t, len << 4 | op, with BAM's codes: I = 1, D = 2, = is 7, X = 8.  Operations are in
+ * WALK order: the read forward, the reference in the orientation it is taken in; A RECORD WITH flags BIT 0 IS REVERSED BY WHOEVER PRINTS
+ * IT (PAF and SAM have the target forward).  For every record: the lengths of = X I add up to qe - qs, those of = X D to te - ts, those of
+ * = to matches, those of X to subst; the first and the last operation are = or X; no two neighbours are equal; every length is at least 1.
+ * cl_cigars_of: the streams of cl_overlaps_of against the arena `refs`.  d_rec_ops (device, rec_cap words): the operation count of every
+ * record, in the order of cl_overlaps_of's records (*n_rec of them); d_ops (device, ops_cap words): the operations of the records one
+ * behind the other (*n_ops).  id_limit (0: every reference): a visit on a reference id at or past it gets the count 0 and no operation —
+ * with id_limit = the pseudo reads of a genome the counts that are not 0 are those of the records cl_mappings_lift keeps, in their order.
+ * On the device (k_cigar_walk): a wave per read as in cl_overlaps_of (max_blocks bounds the grid, 0: four per CU; it changes no result);
+ * run heads from ballots, run lengths from a segmented wave sum; one pass counts, a prefix sum places, the same kernel body fills.
+ * Either capacity too small (or its pointer null): CL_E_CAPACITY, both needs in *n_rec / *n_ops and nothing written.  A malformed stream
+ * is CL_E_INVALID as in cl_overlaps_of; a merged run of 2^28 bases or more inside a record, and 2^32 records or more, CL_E_UNSUPPORTED,
+ * the text naming the read; the counts are 0 then and nothing is handed out. */
+cl_status cl_cigars_of(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint32_t id_limit, uint32_t max_blocks,
+                       uint32_t* d_rec_ops, uint64_t rec_cap, uint64_t* n_rec, uint32_t* d_ops, uint64_t ops_cap, uint64_t* n_ops);
+/* The same on the HOST (references as in cl_edit_profile_host), a sequential walk with the same checks in the same order; the outputs may
+ * be null to ask for the counts.  bad_read / bad_code (optional): the first refused read and its code — those of cl_overlaps_host, and
+ * 256 for the run that does not fit (cl_cigars_error gives the text of either). */
+cl_status cl_cigars_host(const uint8_t* h_ref_codes, const uint64_t* h_ref_off, uint32_t n_refs, const uint8_t* h_es, const uint64_t* h_es_off, uint64_t n_reads, uint32_t id_limit,
+                         uint32_t* h_rec_ops, uint64_t rec_cap, uint64_t* n_rec, uint32_t* h_ops, uint64_t ops_cap, uint64_t* n_ops, uint64_t* bad_read, uint32_t* bad_code);
+const char* cl_cigars_error(uint32_t code);
+/* Opt-in (off by default: one flag test per batch, no launch, no allocation, every output byte the same), on top of cl_ctx_set_mappings:
+ * while both are on, every batch leaves the CIGARs of its lifted records on the host too, made in the mappings' hook with the record
+ * offsets of that batch's walk.  cl_ctx_cigars: those of this context and its compressor's lanes so far, in the order of cl_ctx_mappings'
+ * records — a count per record and the operations (CL_E_CAPACITY with both needs and nothing written when a capacity is too small);
+ * switching the flag on drops what was kept.  Switching it on without cl_ctx_set_mappings is CL_E_INVALID, and so is
+ * cl_compressor_refs_finish when the mappings were switched off again; refused wherever the mappings are (ranks, cl_compress_shard). */
+cl_status cl_ctx_set_cigars(cl_ctx* ctx, int on);
+cl_status cl_ctx_cigars(const cl_ctx* ctx, uint32_t* h_rec_ops, uint64_t rec_cap, uint64_t* n_rec, uint32_t* h_ops, uint64_t ops_cap, uint64_t* n_ops);
+
 /* ---- pileup (no counterpart in the reference) — what a reference-genome run aligned, per genome position ------------- */
 /* The second half of what a -G run aligns: which genome position every read base was aligned to, and what the read said there.  The
  * geometry is that of cl_mappings_lift; the table has n_pos = sum of seq_len[s] positions, sequence s from the sum of the lengths before
@@ -875,6 +910,8 @@ cl_status cl_compressor_overlaps(const cl_compressor* c, cl_overlap* h_out, uint
 cl_status cl_compressor_genome_geometry(cl_compressor* c, const uint64_t* h_seq_len, uint32_t n_seqs, uint32_t read_len, uint32_t overlap);
 /* cl_ctx_mappings of the compressor's context (cl_ctx_set_mappings): after the last cl_compressor_encode, of every chunk */
 cl_status cl_compressor_mappings(const cl_compressor* c, cl_overlap* h_out, uint64_t cap, uint64_t* n_out);
+/* cl_ctx_cigars of the compressor's context (cl_ctx_set_cigars): after the last cl_compressor_encode, of every chunk */
+cl_status cl_compressor_cigars(const cl_compressor* c, uint32_t* h_rec_ops, uint64_t rec_cap, uint64_t* n_rec, uint32_t* h_ops, uint64_t ops_cap, uint64_t* n_ops);
 /* The compressor's table (cl_ctx_set_pileup), finished, after the last cl_compressor_encode: *out belongs to the compressor and goes
  * with it.  CL_E_INVALID: the flag was off when the references were finished, or chunks are still to be coded. */
 cl_status cl_compressor_pileup(cl_compressor* c, cl_pileup** out);
