@@ -322,8 +322,12 @@ extern "C" cl_status cl_candidates_at(cl_ctx* ctx, const cl_index* X, const cl_k
 		HIP_TRY(ctx, hipMemcpyAsync(h_poff_at.data(), at.p, ((size_t)nr + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	}
-	const uint64_t MAX_PAIRS = 1ull << 27;                  // pairs per batch (1 GiB of keys + sort scratch)
-	const uint32_t MAX_READS = 1u << (40 - ref_bits > 31 ? 31 : 40 - ref_bits);   // keep keys within 40 bits => 5 radix passes
+	uint64_t MAX_PAIRS = 1ull << 27;                        // pairs per batch (1 GiB of keys + sort scratch)
+	uint32_t MAX_READS = 1u << (40 - ref_bits > 31 ? 31 : 40 - ref_bits);   // keep keys within 40 bits => 5 radix passes
+	// COLORD_HIP_CAND_PAIRS / COLORD_HIP_CAND_READS lower the two limits so that small test inputs are cut into several batches
+	// (a read is never split: a batch holds at least one read whatever its pair count)
+	if (const char* e = getenv("COLORD_HIP_CAND_PAIRS")) { const uint64_t v = strtoull(e, nullptr, 10); if (v) MAX_PAIRS = v; }
+	if (const char* e = getenv("COLORD_HIP_CAND_READS")) { const uint64_t v = strtoull(e, nullptr, 10); if (v && v < MAX_READS) MAX_READS = (uint32_t)v; }
 	uint32_t r0 = 0;
 	DevBuf<uint64_t> pairs; DevBuf<uint32_t> hf, head_pos, votes; DevBuf<uint64_t> ukey;
 	while (r0 < nr)

@@ -524,6 +524,17 @@ class Context:
         _check(self, self.lib.cl_candidates(self.h, index.h, lists.h, c, refs.data_ptr(), votes.data_ptr(), cnt.data_ptr()))
         return refs, votes, cnt
 
+    def candidates_at(self, index, lists, bounds: torch.Tensor, c: int):
+        """The query of one chunk of reads against an index over the whole input: bounds[i] = reference reads before read i of `lists`."""
+        n = lists.n_reads
+        bounds = bounds.to(self.device).contiguous()
+        assert bounds.dtype == torch.int32 and bounds.numel() == n + 1
+        refs = torch.empty((n, c), dtype=torch.int32, device=self.device)
+        votes = torch.empty((n, c), dtype=torch.int32, device=self.device)
+        cnt = torch.empty(n, dtype=torch.int32, device=self.device)
+        _check(self, self.lib.cl_candidates_at(self.h, index.h, lists.h, bounds.data_ptr(), c, refs.data_ptr(), votes.data_ptr(), cnt.data_ptr()))
+        return refs, votes, cnt
+
     def candidates_common(self, index, lists, c: int, refs, cnt):
         n = lists.n_reads
         off = torch.empty(n * c + 1, dtype=torch.int64, device=self.device)
