@@ -251,6 +251,14 @@ _SIG = {
     "cl_ctx_set_cigars": (C.c_int32, [_P, C.c_int]),
     "cl_ctx_cigars": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64), _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cl_compressor_cigars": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64), _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cl_cigars_pack": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cl_cigars_pack_host": (C.c_int32, [_P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cl_cigars_unpack_host": (C.c_int32, [_P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cl_cigars_check_host": (C.c_uint32, [_P, C.c_uint64]),
+    "cl_cigars_refusal": (C.c_char_p, [C.c_uint32]),
+    "cl_ctx_set_cigars_coded": (C.c_int32, [_P, C.c_int]),
+    "cl_ctx_cigars_coded": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64), _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cl_compressor_cigars_coded": (C.c_int32, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64), _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cl_compressor_genome_geometry": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "cl_pileup_create": (C.c_int32, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "cl_pileup_free": (None, [_P]),

@@ -28,6 +28,7 @@
 #include "objects.hpp"
 #include "es_wave.hpp"
 #include "cigars.hpp"
+#include "cigar_coder.hpp"
 #include "compressor.hpp"
 #include <algorithm>
 #include <mutex>
@@ -300,6 +301,7 @@ extern "C" cl_status cl_ctx_set_cigars(cl_ctx* c, int on)
 		for (cl_ctx* lane : c->lanes) { std::lock_guard<std::mutex> ll(lane->cigars_mu); lane->cigar_recs.clear(); }
 	}
 	c->cigars = on != 0;
+	if (!on) c->cigars_coded = false;                                          // (the coded form is a form of these)
 	return CL_OK;
 }
 extern "C" cl_status cl_ctx_cigars(const cl_ctx* c, uint32_t* h_rec_ops, uint64_t rec_cap, uint64_t* n_rec, uint32_t* h_ops, uint64_t ops_cap, uint64_t* n_ops)
@@ -314,15 +316,22 @@ extern "C" cl_status cl_ctx_cigars(const cl_ctx* c, uint32_t* h_rec_ops, uint64_
 	for (const cl_ctx* lane : c->lanes) take(lane);
 	std::sort(parts.begin(), parts.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
 	uint64_t nr = 0, no = 0;
-	for (const auto& p : parts) { nr += p.second->rec_ops.size(); no += p.second->ops.size(); }
+	for (const auto& p : parts) { nr += p.second->rec_ops.size(); no += p.second->ops.size() + p.second->coded_ops; }
 	*n_rec = nr; *n_ops = no;
 	if (nr > rec_cap || (nr && !h_rec_ops) || no > ops_cap || (no && !h_ops)) return CL_E_CAPACITY;
 	uint64_t ar = 0, ao = 0;
+	std::vector<uint32_t> dec;
 	for (const auto& p : parts)
 	{
 		if (!p.second->rec_ops.empty()) memcpy(h_rec_ops + ar, p.second->rec_ops.data(), p.second->rec_ops.size() * 4);
 		if (!p.second->ops.empty()) memcpy(h_ops + ao, p.second->ops.data(), p.second->ops.size() * 4);
-		ar += p.second->rec_ops.size(); ao += p.second->ops.size();
+		if (p.second->coded_ops)
+		{	// a batch kept coded (cl_ctx_set_cigars_coded): decoded here, on the host
+			dec.clear();
+			if (cgc_unpack(p.second->coded.data(), p.second->coded.size(), dec) != CGC_OK || dec.size() != p.second->coded_ops) return CL_E_INVALID;
+			memcpy(h_ops + ao, dec.data(), dec.size() * 4);
+		}
+		ar += p.second->rec_ops.size(); ao += p.second->ops.size() + p.second->coded_ops;
 	}
 	return CL_OK;
 }
@@ -343,9 +352,11 @@ cl_status cigars_chunk(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, c
 		DevBuf<uint32_t> rec_ops, ops; uint64_t n_ops = 0; bool filled = false;
 		CL_TRY(cg_run(ctx, refs, d_es, d_es_off, n_reads, id_limit, 0, d_rec_off, n_rec, rec_ops, nullptr, 0, &ops, &n_ops, &filled));
 		std::vector<uint32_t> all(n_rec);
-		B.ops.resize(n_ops);
+		const bool coded = ctx->cigars_coded;                                    // the operations stay on the device: their segments come instead (cigar_coder.hip)
+		if (coded) { CL_TRY(cigars_pack_device(ctx, "cl_ctx_set_cigars_coded", ops.p, n_ops, 0, 0, B.coded, &B.coded_segments, &B.coded_escapes)); B.coded_ops = n_ops; }
+		else B.ops.resize(n_ops);
 		HIP_TRY(ctx, hipMemcpyAsync(all.data(), rec_ops.p, n_rec * 4, hipMemcpyDeviceToHost, cl_launch_stream(ctx)));
-		if (n_ops) HIP_TRY(ctx, hipMemcpyAsync(B.ops.data(), ops.p, n_ops * 4, hipMemcpyDeviceToHost, cl_launch_stream(ctx)));
+		if (n_ops && !coded) HIP_TRY(ctx, hipMemcpyAsync(B.ops.data(), ops.p, n_ops * 4, hipMemcpyDeviceToHost, cl_launch_stream(ctx)));
 		HIP_TRY(ctx, hipStreamSynchronize(cl_launch_stream(ctx)));
 		for (uint32_t c : all) if (c) B.rec_ops.push_back(c);
 	}

@@ -3,18 +3,37 @@
 // --cigar` as the PAF of --mappings with cg:Z: appended and by `info --mappings --sam` as SAM, without decoding `dna` or `qual` and without a GPU.
 // One part, little-endian:
 //   u32 version = 1, u32 operation size = 4, u64 records, u64 operations, then the u32 counts per record, then the operations
+// or, written with --cigars-coded, the operations as the segments of ../cigar_coder.hpp, coded on the device:
+//   u32 version = 2, u32 operation size = 4, u64 records, u64 operations, u64 segments, u64 segment bytes, the u32 counts per record, the segments
+// Both versions are read into the same CigarSet; a version-2 stream is decoded first (cgc_unpack refuses what is no whole segments of its format),
+// then every check below runs as for version 1.
 // An operation is len << 4 | op with BAM's codes (I 1, D 2, = 7, X 8), in WALK order: the operations of a record taken reversed are reversed here,
 // where they are printed.  The reference's decompressor finds its streams by name and never sees this one; `decompress` and `check` ignore it.
 // The reader holds every record's operations against its mapping record (cigars.hpp: cg_check) and refuses a stream that breaks one relation.
 #pragma once
 #include "mappings_stream.hpp"
 #include "../cigars.hpp"
+#include "../cigar_coder.hpp"
 
 struct CigarSet {
 	std::vector<uint32_t> rec_ops, ops;                                        // a count per record of the mappings, the operations one behind the other
 	std::vector<uint64_t> off;                                                 // unpack: where a record's operations start (records + 1 entries)
 	static constexpr uint32_t VERSION = 1;
 	static constexpr size_t HEAD = 24;
+	static constexpr uint32_t VERSION_CODED = 2;
+	static constexpr size_t HEAD_CODED = 40;
+	uint32_t version = VERSION;                                                // unpack: the version that was read
+	uint64_t coded_bytes = 0, coded_segments = 0, coded_escapes = 0;           // ... and of a version-2 stream, its segments
+	// version 2: the counts and the coded segments of n_ops operations
+	static std::vector<uint8_t> pack_coded(const std::vector<uint32_t>& rec_ops, const std::vector<uint8_t>& segments, uint64_t n_ops, uint64_t n_segments)
+	{
+		std::vector<uint8_t> v; v.reserve(HEAD_CODED + rec_ops.size() * 4 + segments.size());
+		auto le = [&](uint64_t x, int n) { for (int i = 0; i < n; ++i) v.push_back((uint8_t)(x >> (8 * i))); };
+		le(VERSION_CODED, 4); le(CG_OP_BYTES, 4); le(rec_ops.size(), 8); le(n_ops, 8); le(n_segments, 8); le(segments.size(), 8);
+		for (uint32_t c : rec_ops) le(c, 4);
+		v.insert(v.end(), segments.begin(), segments.end());
+		return v;
+	}
 	std::vector<uint8_t> pack() const
 	{
 		std::vector<uint8_t> v; v.reserve(HEAD + (rec_ops.size() + ops.size()) * 4);
@@ -31,12 +50,28 @@ struct CigarSet {
 		rec_ops.clear(); ops.clear(); off.clear();
 		if (v.size() < HEAD) return false;
 		auto le = [&](size_t at, int n) { uint64_t x = 0; for (int i = 0; i < n; ++i) x |= (uint64_t)v[at + i] << (8 * i); return x; };
-		if (le(0, 4) != VERSION || le(4, 4) != CG_OP_BYTES) return false;
-		const uint64_t nr = le(8, 8), no = le(16, 8), words = (v.size() - HEAD) / 4;
-		if ((v.size() - HEAD) % 4 || nr > words || no != words - nr || nr != M.recs.size()) return false;      // (nothing is reserved for a count the bytes cannot hold)
-		rec_ops.resize(nr); ops.resize(no); off.assign(nr + 1, 0);
-		for (uint64_t i = 0; i < nr; ++i) { rec_ops[i] = (uint32_t)le(HEAD + 4 * i, 4); off[i + 1] = off[i] + rec_ops[i]; }
-		for (uint64_t i = 0; i < no; ++i) ops[i] = (uint32_t)le(HEAD + 4 * (nr + i), 4);
+		version = (uint32_t)le(0, 4); coded_bytes = coded_segments = coded_escapes = 0;
+		if ((version != VERSION && version != VERSION_CODED) || le(4, 4) != CG_OP_BYTES) return false;
+		const uint64_t nr = le(8, 8), no = le(16, 8);
+		if (version == VERSION_CODED)
+		{	// the sizes against the bytes, the segments decoded, their counts against the header
+			if (v.size() < HEAD_CODED) return false;
+			const uint64_t ns = le(24, 8), nb = le(32, 8), rest = v.size() - HEAD_CODED;
+			if (nr > rest / 4 || nb != rest - 4 * nr || nr != M.recs.size() || no > nb * (uint64_t)CGC_SEG_OPS) return false;      // (nothing is reserved for a count the bytes cannot hold)
+			uint64_t got_seg = 0, got_esc = 0;
+			if (cgc_unpack(v.data() + HEAD_CODED + 4 * nr, nb, ops, &got_seg, &got_esc) != CGC_OK || ops.size() != no || got_seg != ns) { ops.clear(); return false; }
+			coded_bytes = nb; coded_segments = ns; coded_escapes = got_esc;
+			rec_ops.resize(nr); off.assign(nr + 1, 0);
+			for (uint64_t i = 0; i < nr; ++i) { rec_ops[i] = (uint32_t)le(HEAD_CODED + 4 * i, 4); off[i + 1] = off[i] + rec_ops[i]; }
+		}
+		else
+		{
+			const uint64_t words = (v.size() - HEAD) / 4;
+			if ((v.size() - HEAD) % 4 || nr > words || no != words - nr || nr != M.recs.size()) return false;      // (nothing is reserved for a count the bytes cannot hold)
+			rec_ops.resize(nr); ops.resize(no); off.assign(nr + 1, 0);
+			for (uint64_t i = 0; i < nr; ++i) { rec_ops[i] = (uint32_t)le(HEAD + 4 * i, 4); off[i + 1] = off[i] + rec_ops[i]; }
+			for (uint64_t i = 0; i < no; ++i) ops[i] = (uint32_t)le(HEAD + 4 * (nr + i), 4);
+		}
 		bool ok = off[nr] == no;
 		for (uint64_t i = 0; ok && i < nr; ++i) ok = M.recs[i].qe <= M.recs[i].qlen && cg_check(M.recs[i], ops.data() + off[i], rec_ops[i]) == 0;      // (qe <= qlen: the hard clips of SAM)
 		if (!ok) { rec_ops.clear(); ops.clear(); off.clear(); }
@@ -70,8 +105,10 @@ inline int read_hipcigars(const std::string& path, const MappingSet& M, CigarSet
 	ar.close();
 	return r;
 }
-// ... and its header alone, for the line of `colord_hip info`: 0 none, 1 read, -1 the bytes are not a version-1 header
-inline int peek_hipcigars(const std::string& path, uint64_t& records, uint64_t& operations)
+// ... and its header alone, for the line of `colord_hip info`: 0 none, 1 read, -1 the bytes are not a header of version 1 or 2 (of version 2: with
+// segment headers that fit the bytes and add up to the operations; *coded takes what they say)
+struct CigarCoded { uint32_t version = 0; uint64_t bytes = 0, segments = 0, escapes = 0; };
+inline int peek_hipcigars(const std::string& path, uint64_t& records, uint64_t& operations, CigarCoded* coded = nullptr)
 {
 	ArchiveReader ar;
 	if (!ar.open(path)) return 0;
@@ -80,7 +117,21 @@ inline int peek_hipcigars(const std::string& path, uint64_t& records, uint64_t& 
 	if (s >= 0)
 	{
 		auto le = [&](size_t at, int n) { uint64_t x = 0; for (int i = 0; i < n; ++i) x |= (uint64_t)b[at + i] << (8 * i); return x; };
-		r = ar.part(s, 0, b, meta) && b.size() >= CigarSet::HEAD && le(0, 4) == CigarSet::VERSION && le(4, 4) == CG_OP_BYTES ? 1 : -1;
+		r = ar.part(s, 0, b, meta) && b.size() >= CigarSet::HEAD && (le(0, 4) == CigarSet::VERSION || le(0, 4) == CigarSet::VERSION_CODED) && le(4, 4) == CG_OP_BYTES ? 1 : -1;
+		if (r > 0 && le(0, 4) == CigarSet::VERSION_CODED)
+		{
+			CigarCoded c; c.version = 2;
+			uint64_t no = 0;
+			const uint64_t nr = b.size() >= CigarSet::HEAD_CODED ? le(8, 8) : 0, rest = b.size() >= CigarSet::HEAD_CODED ? b.size() - CigarSet::HEAD_CODED : 0;
+			if (b.size() < CigarSet::HEAD_CODED || nr > rest / 4 || le(32, 8) != rest - 4 * nr) r = -1;
+			else
+			{
+				c.bytes = le(32, 8);
+				if (cgc_scan(b.data() + CigarSet::HEAD_CODED + 4 * nr, c.bytes, &no, &c.segments, &c.escapes) != CGC_OK || no != le(16, 8) || c.segments != le(24, 8)) r = -1;
+			}
+			if (r > 0 && coded) *coded = c;
+		}
+		else if (r > 0 && coded) coded->version = 1;
 		if (r > 0) { records = le(8, 8); operations = le(16, 8); }
 	}
 	ar.close();

@@ -209,6 +209,7 @@ int run_compress(int argc, char** argv)
 	if (O.overlaps) cl_ctx_set_overlaps(ctx, 1);
 	if (O.mappings) cl_ctx_set_mappings(ctx, 1);
 	if (O.cigars) ck(ctx, cl_ctx_set_cigars(ctx, 1), "cl_ctx_set_cigars");
+	if (O.cigars_coded) ck(ctx, cl_ctx_set_cigars_coded(ctx, 1), "cl_ctx_set_cigars_coded");
 	if (O.pileup) cl_ctx_set_pileup(ctx, 1);
 	std::vector<uint64_t> report_lens;                         // --report: every read length, as the reader hands the reads over in pass 1 (N50 / N90)
 	ck(ctx, cl_compressor_create(ctx, qctx, &prm.cp, with_qual ? &prm.qp : nullptr, nullptr, estimated_bases(R), &cmp), "cl_compressor_create");
@@ -391,8 +392,8 @@ int run_compress(int argc, char** argv)
 		if (O.cigars)
 		{
 			CigarSet G;
-			add_cigars(ar, ctx, cmp, V, G);
-			if (O.verbose) fprintf(stderr, "# cigars: %zu operations of %zu records, %zu bytes\n", G.ops.size(), G.rec_ops.size(), CigarSet::HEAD + 4 * (G.ops.size() + G.rec_ops.size()));
+			const size_t bytes = add_cigars(ar, ctx, cmp, V, G, O.cigars_coded);
+			if (O.verbose) fprintf(stderr, "# cigars: %zu operations of %zu records, %zu bytes%s\n", G.ops.size(), G.rec_ops.size(), bytes, O.cigars_coded ? " (coded)" : "");
 		}
 	}
 	if (O.pileup)

@@ -379,9 +379,22 @@ inline void add_mappings(ArchiveWriter& ar, MappingSet& S, const GenomeMode& GM,
 }
 // --cigars: the `hipcigars` stream (cigars_stream.hpp), before finish_archive: the CIGARs the compressor's context and its lanes kept, in the order
 // of the mapping records S; what is written is what the reader will accept
-inline void add_cigars(ArchiveWriter& ar, cl_ctx* ctx, cl_compressor* cmp, const MappingSet& S, CigarSet& G)
+// coded (--cigars-coded): the record counts and the segments the device coded (version 2); the writer decodes what it wrote, into G.  Returns the stream's bytes.
+inline size_t add_cigars(ArchiveWriter& ar, cl_ctx* ctx, cl_compressor* cmp, const MappingSet& S, CigarSet& G, bool coded)
 {
 	uint64_t nr = 0, no = 0;
+	if (coded)
+	{
+		uint64_t nb = 0, ns = 0;
+		const cl_status s = cl_compressor_cigars_coded(cmp, nullptr, 0, &nr, nullptr, 0, &nb, &no, &ns);
+		if (s != CL_OK && s != CL_E_CAPACITY) ck(ctx, s, "cl_compressor_cigars_coded");
+		std::vector<uint32_t> rec_ops(nr); std::vector<uint8_t> seg(nb);
+		if (nr || nb) ck(ctx, cl_compressor_cigars_coded(cmp, rec_ops.data(), nr, &nr, seg.data(), nb, &nb, &no, &ns), "cl_compressor_cigars_coded");
+		const std::vector<uint8_t> b = CigarSet::pack_coded(rec_ops, seg, no, ns);
+		if (!G.unpack(b, S)) die("internal: the coded CIGARs do not decode to CIGARs that fit the mapping records");
+		ar.add(ar.reg("hipcigars"), b.data(), b.size(), 0);
+		return b.size();
+	}
 	const cl_status s = cl_compressor_cigars(cmp, nullptr, 0, &nr, nullptr, 0, &no);
 	if (s != CL_OK && s != CL_E_CAPACITY) ck(ctx, s, "cl_compressor_cigars");
 	G.rec_ops.resize(nr); G.ops.resize(no);
@@ -390,6 +403,7 @@ inline void add_cigars(ArchiveWriter& ar, cl_ctx* ctx, cl_compressor* cmp, const
 	CigarSet back;
 	if (!back.unpack(b, S)) die("internal: the CIGARs do not fit the mapping records");
 	ar.add(ar.reg("hipcigars"), b.data(), b.size(), 0);
+	return b.size();
 }
 // --pileup: the `hippileup` stream (pileup_stream.hpp), before finish_archive: the geometry, the thresholds, the totals of the compressor's table, the genome's
 // sequence names and lengths, and the table's sites — the table itself is the size of the genome and stays on the device

@@ -321,9 +321,14 @@ int run_info(int argc, char** argv)
 		fprintf(stderr, "mappings: %llu records of reads against the %zu sequences of the reference genome (`colord_hip info --mappings [--min-block N] [--names]` prints them as PAF, `--mappings --coverage W` a coverage track, `--mappings --summary [--json]` what they add up to)\n",
 			(unsigned long long)mps.recs.size(), mps.seq_len.size());
 	else if (have < 0) fprintf(stderr, "mappings: a `hipmappings` stream this build cannot read\n");
-	uint64_t cg_records = 0, cg_operations = 0;
-	if (const int have = peek_hipcigars(path, cg_records, cg_operations); have > 0)
-		fprintf(stderr, "cigars: %llu operations of %llu mapping records (`colord_hip info --mappings --cigar` prints the PAF with cg:Z:, `--mappings --sam` SAM)\n", (unsigned long long)cg_operations, (unsigned long long)cg_records);
+	uint64_t cg_records = 0, cg_operations = 0; CigarCoded cg_coded;
+	if (const int have = peek_hipcigars(path, cg_records, cg_operations, &cg_coded); have > 0)
+	{
+		fprintf(stderr, "cigars: %llu operations of %llu mapping records", (unsigned long long)cg_operations, (unsigned long long)cg_records);
+		if (cg_coded.version == 2) fprintf(stderr, ", coded: %llu bytes in %llu segments, %.3f bytes per operation, %llu escapes", (unsigned long long)cg_coded.bytes, (unsigned long long)cg_coded.segments,
+			cg_operations ? (double)cg_coded.bytes / (double)cg_operations : 0.0, (unsigned long long)cg_coded.escapes);
+		fprintf(stderr, " (`colord_hip info --mappings --cigar` prints the PAF with cg:Z:, `--mappings --sam` SAM)\n");
+	}
 	else if (have < 0) fprintf(stderr, "cigars: a `hipcigars` stream this build cannot read\n");
 	PileupSet pil;
 	if (const int have = read_hippileup(path, pil); have > 0)

@@ -45,6 +45,7 @@ struct Options {
 	bool sketch = false; long sketch_size = -1, sketch_min_count = -1;   // --sketch [--sketch-size N] [--sketch-min-count M]: the MinHash sketch of the k-mers pass 1 counted at least M times (cl_ctx_set_kmer_sketch) in a `hipsketch` stream; defaults 10 000 and 2
 	bool mappings = false;                          // --mappings (with -G): the read-to-genome alignments the edit scripts hold (cl_ctx_set_mappings) in a `hipmappings` stream
 	bool cigars = false;                            // --cigars (with --mappings): the base-level CIGAR of every mapping record (cl_ctx_set_cigars) in a `hipcigars` stream
+	bool cigars_coded = false;                      // --cigars-coded (with --cigars): the operations are coded on the device (cl_ctx_set_cigars_coded); `hipcigars` version 2
 	bool pileup = false; long pileup_min_depth = -1, pileup_min_alt = -1; double pileup_min_frac = -1;   // --pileup (with -G) [--pileup-min-depth N] [--pileup-min-alt N] [--pileup-min-frac F]: the per-position base counts of the reads on the genome's pieces (cl_ctx_set_pileup); their sites in a `hippileup` stream; defaults 4, 3 and 0.25
 	bool overlaps = false;                          // --overlaps: the read-to-read overlaps the edit scripts hold (cl_ctx_set_overlaps) in a `hipoverlaps` stream
 	uint64_t qual_domain_symbols = 0;               // --qual-domain-symbols N: the quality models start afresh about every N symbols (cl_compressor_set_qual_domain_symbols; stream `hipqdomains`)
@@ -149,9 +150,13 @@ inline void usage()
 		"                     cg:Z: appended, `info --mappings --sam` SAM (a line per record; the second and later records of a read are supplementary, unaligned read ends are hard clips,\n"
 		"                     no sequence); neither decodes `dna` or `qual` or needs a GPU.  NOT COMPRESSED: THE STREAM IS LARGER THAN THE `dna` STREAM — measured on an\n"
 		"                     MI355X, 300 Mbases of synthetic ONT reads on a 15-Mbase genome: 39.5 M operations, 158 MB, 0.53 bytes per input base, 7.5 times the `dna` stream and 63 percent\n"
-		"                     of the archive; 2.55 s from file to archive against 2.16 s with --mappings alone.  It is opt-in; a compressed operation format is the follow-up.\n"
+		"                     of the archive; 2.55 s from file to archive against 2.16 s with --mappings alone.  It is opt-in; --cigars-coded stores it coded.\n"
 		"                     = and X are not collapsed to M.  `decompress` / `check` ignore the stream.  Not without --mappings, and so not with\n"
 		"                     --gpus > 1, --domains > 1 or --overlaps (DESIGN.md 4o, 9)\n"
+		"  --cigars-coded     with --cigars: the operations are coded ON THE DEVICE before they leave it (stream `hipcigars` version 2): an op symbol in the context of the op before and a\n"
+		"                     length symbol in the context of its op (lengths above 255 escape to a raw u32), a static table per segment of 2^20 operations, the interval coder of the\n"
+		"                     `dna` and `qual` streams over parts of 4096 operations.  `info --mappings --cigar | --sam` print the same text from either version; `colord_hip info` adds the coded\n"
+		"                     bytes, bytes per operation and the escapes.  On the run above: 18.3 MB instead of 158 MB (0.46 bytes per operation, 0.87 times the `dna` stream), 3.05 s against 2.53 s.  Without it every byte is as before.  Not made for HiFi-like inputs, whose = runs are mostly escapes (DESIGN.md 4p)\n"
 		"  --pileup           with -G: per-position base counts of the reads on the genome, made on the device from the edit scripts: for every genome position the read columns that match, that say\n"
 		"                     A, C, G or T instead (in the genome's forward orientation), that delete it, and the insertion RUNS left of which it lies (a run counts once: unaligned read ends are\n"
 		"                     coded as long runs).  THE FULL TABLE IS NOT STORED, it is the size of the genome: the archive gets its totals and its SITES (stream `hippileup`, 48 bytes per site and\n"
@@ -236,6 +241,7 @@ inline Options parse_options(int argc, char** argv)
 		else if (a == "--overlaps") O.overlaps = true;
 		else if (a == "--mappings") O.mappings = true;
 		else if (a == "--cigars") O.cigars = true;
+		else if (a == "--cigars-coded") O.cigars_coded = true;
 		else if (a == "--pileup") O.pileup = true;
 		else if (a == "--pileup-min-depth") { O.pileup_min_depth = atol(need(i).c_str()); if (O.pileup_min_depth < 0 || O.pileup_min_depth > 0x7fffffffl) die("--pileup-min-depth must be in [0, 2147483647]"); }
 		else if (a == "--pileup-min-alt") { O.pileup_min_alt = atol(need(i).c_str()); if (O.pileup_min_alt < 0 || O.pileup_min_alt > 0x7fffffffl) die("--pileup-min-alt must be in [0, 2147483647]"); }
@@ -283,6 +289,7 @@ inline Options parse_options(int argc, char** argv)
 		if (O.overlaps) die("--mappings is not available with --overlaps (which refuses -G)");
 	}
 	if (O.cigars && !O.mappings) die("--cigars needs --mappings (with -G): its CIGARs are those of the mapping records");
+	if (O.cigars_coded && !O.cigars) die("--cigars-coded needs --cigars (with --mappings and -G): it is a form of their stream");
 	if (!O.pileup && (O.pileup_min_depth >= 0 || O.pileup_min_alt >= 0 || O.pileup_min_frac >= 0)) { usage(); die("--pileup-min-depth, --pileup-min-alt and --pileup-min-frac need --pileup"); }
 	if (O.pileup)
 	{	// a column lies on a piece of the reference genome, placed by ONE geometry in ONE table on ONE device

@@ -366,7 +366,8 @@ struct cl_ctx {
 	std::map<uint64_t, std::vector<cl_overlap>> mapping_recs;   // ... by the batch's first read (under mappings_mu: cl_ctx_mappings merges the encode lanes')
 	mutable std::mutex mappings_mu;
 	bool cigars = false;                         // cl_ctx_set_cigars (with mappings): the mappings hook keeps the CIGAR of every lifted record too (cigars.hip)
-	struct CigarBatch { std::vector<uint32_t> rec_ops, ops; };   // a count per lifted record of a batch, and the operations one behind the other
+	bool cigars_coded = false;                   // cl_ctx_set_cigars_coded (with cigars): a batch's operations are coded on the device (cigar_coder.hip) and kept as segment bytes
+	struct CigarBatch { std::vector<uint32_t> rec_ops, ops; std::vector<uint8_t> coded; uint64_t coded_ops = 0, coded_segments = 0, coded_escapes = 0; };   // a count per lifted record of a batch, and the operations one behind the other — raw, or (cigars_coded) as the segments of cigar_coder.hpp
 	std::map<uint64_t, CigarBatch> cigar_recs;   // ... by the batch's first read (under cigars_mu: cl_ctx_cigars merges the encode lanes')
 	mutable std::mutex cigars_mu;
 	bool pileup = false;                         // cl_ctx_set_pileup: tuple_streams (pass_steps.hpp) adds every batch on genome pieces to the compressor's table (pileup.hip)

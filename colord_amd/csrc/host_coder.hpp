@@ -23,10 +23,11 @@ namespace hostrc {
 struct RangeDec {
 	static constexpr uint64_t TOP = 0x00ffffffffffffULL, MASK = 0xff00000000000000ULL;
 	uint64_t low = 0, range = 0, buffer = 0; const uint8_t* in = nullptr; uint64_t n = 0, pos = 0;
-	uint8_t byte() { return pos < n ? in[pos++] : 0; }
+	uint64_t over = 0;                                                   // bytes asked for past the input's end (read as 0): a caller that knows its part's size checks it
+	uint8_t byte() { if (pos < n) return in[pos++]; ++over; return 0; }
 	void start(const uint8_t* p, uint64_t len)                         // SetInput + Start (sub_rc.h:249-262)
 	{
-		in = p; n = len; pos = 0; buffer = 0;
+		in = p; n = len; pos = 0; buffer = 0; over = 0;
 		for (int i = 1; i <= 8; ++i) buffer |= (uint64_t)byte() << (64 - 8 * i);
 		low = 0; range = MASK;
 	}

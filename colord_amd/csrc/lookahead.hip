@@ -39,6 +39,7 @@ template<class Work> static cl_status work_on(cl_compressor* c, cl_ctx* ctx, Wor
 	ctx->overlaps = c->ctx->overlaps;
 	ctx->mappings = c->ctx->mappings;
 	ctx->cigars = c->ctx->cigars;
+	ctx->cigars_coded = c->ctx->cigars_coded;
 	ctx->pileup = c->ctx->pileup;
 	const cl_status s = work();
 	cl_timing_collect(ctx);

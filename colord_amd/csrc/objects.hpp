@@ -86,6 +86,9 @@ cl_status overlaps_offsets(cl_ctx* ctx, const char* who, const cl_reads* refs, c
 // record offsets per read and record count (overlaps_records); n_lifted: the records the lift kept
 cl_status cigars_chunk(cl_ctx* ctx, const cl_reads* refs, const uint8_t* d_es, const uint64_t* d_es_off, uint32_t n_reads, uint64_t first_read, uint32_t id_limit, const uint64_t* d_rec_off,
                        uint64_t n_rec, uint64_t n_lifted);
+// cigar_coder.hip (cl_cigars_pack, and cigars_chunk under cl_ctx_set_cigars_coded): the segments (cigar_coder.hpp) of n_ops words in device memory appended
+// to out; a knob of 0 is its default; out is unchanged when the call fails
+cl_status cigars_pack_device(cl_ctx* ctx, const char* who, const uint32_t* d_ops, uint64_t n_ops, uint32_t part_ops, uint32_t seg_ops, std::vector<uint8_t>& out, uint64_t* n_segments, uint64_t* n_escapes);
 // mappings.hip (cl_ctx_set_mappings): the records of a batch whose target is a piece of the reference genome, lifted to the genome's sequences
 // (geom: mappings.hpp, tables on the device; null is an error) and kept on the host by the context that made them
 struct MapGeom;

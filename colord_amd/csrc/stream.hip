@@ -344,6 +344,7 @@ extern "C" cl_status cl_compressor_refs_finish(cl_compressor* c)
 	}
 	// the CIGARs are those of the mapping records: made in their hook, refused wherever they are
 	if (ctx->cigars && !ctx->mappings) return cl_fail(ctx, CL_E_INVALID, "cl_ctx_set_cigars: needs the mapping records (cl_ctx_set_mappings)");
+	if (ctx->cigars_coded && !ctx->cigars) return cl_fail(ctx, CL_E_INVALID, "cl_ctx_set_cigars_coded: needs the CIGARs (cl_ctx_set_cigars)");
 	if (ctx->pileup)
 	{	// a column lies on a piece of the genome, placed by the geometry: one rank, pseudo reads, and the geometry they were cut by
 		if (c->world > 1) return cl_fail(ctx, CL_E_UNSUPPORTED, "cl_ctx_set_pileup: not with reads sharded over ranks (the tables of the ranks are not added yet)");

@@ -62,6 +62,7 @@ class _OrderedLib:
                   "cl_overlaps_host", "cl_ctx_set_overlaps", "cl_ctx_overlaps", "cl_compressor_overlaps",
                   "cl_mappings_lift_host", "cl_ctx_set_mappings", "cl_ctx_mappings", "cl_compressor_mappings",
                   "cl_cigars_host", "cl_cigars_error", "cl_ctx_set_cigars", "cl_ctx_cigars", "cl_compressor_cigars",
+                  "cl_cigars_pack_host", "cl_cigars_unpack_host", "cl_cigars_check_host", "cl_cigars_refusal", "cl_ctx_set_cigars_coded", "cl_ctx_cigars_coded", "cl_compressor_cigars_coded",
                   "cl_pileup_host", "cl_pileup_positions", "cl_ctx_set_pileup")
 
     def __init__(self, lib, device):
@@ -281,6 +282,31 @@ class Context:
     def cigars(self):
         """cl_ctx_cigars: (a count per record of mappings(), the operations one behind the other), two uint32 arrays."""
         return _cigar_records(self.lib.cl_ctx_cigars, self.h)
+
+    def cigars_pack(self, ops: torch.Tensor, part_ops: int = 0, seg_ops: int = 0, cap: "int | None" = None) -> bytes:
+        """cl_cigars_pack: the operation words in `ops` (an int32 tensor on the device, the bits of uint32) as the bytes of their coded segments
+        (DESIGN.md 4p); a knob of 0 is its default.  With `cap` the call is made once with that room (CL_E_CAPACITY raises); without, the need
+        is asked for first.  A word that is no operation raises CL_E_INVALID, the text naming its index."""
+        ops = ops.contiguous()
+        n, nb = ops.numel(), C.c_uint64(0)
+        args = (self.h, ops.data_ptr() if n else None, n, part_ops, seg_ops)
+        if cap is None:
+            st = self.lib.cl_cigars_pack(*args, None, 0, C.byref(nb))
+            if st not in (N.CL_OK, N.CL_E_CAPACITY):
+                _check(self, st)
+            cap = nb.value
+        out = np.zeros(max(cap, 1), np.uint8)
+        _check(self, self.lib.cl_cigars_pack(*args, out.ctypes.data, cap, C.byref(nb)))
+        return out[:nb.value].tobytes()
+
+    def set_cigars_coded(self, on: bool = True):
+        """cl_ctx_set_cigars_coded: on top of set_cigars, a batch's operations are coded on the device and kept as segment bytes; refused
+        without set_cigars."""
+        _check(self, self.lib.cl_ctx_set_cigars_coded(self.h, int(bool(on))))
+
+    def cigars_coded(self):
+        """cl_ctx_cigars_coded: (a count per record of mappings(), the coded segments of all batches, their operations, their segments)."""
+        return _cigar_coded(self.lib.cl_ctx_cigars_coded, self.h)
 
     def set_mappings(self, on: bool = True):
         """cl_ctx_set_mappings: every batch of tuple streams made by a compressor of this context (one with pseudo reads and their geometry)
@@ -995,9 +1021,53 @@ def _cigar_records(fn, h):
     return rec[:nr.value], ops[:no.value]
 
 
+def _cigar_coded(fn, h):
+    """the coded CIGARs a context or a compressor keeps (cl_ctx_cigars_coded / cl_compressor_cigars_coded): the needs first, then that many"""
+    nr, nb, no, ns = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    st = fn(h, None, 0, C.byref(nr), None, 0, C.byref(nb), C.byref(no), C.byref(ns))
+    if st not in (N.CL_OK, N.CL_E_CAPACITY):
+        _check(None, st)
+    rec, raw = np.zeros(nr.value, np.uint32), np.zeros(max(nb.value, 1), np.uint8)
+    if nr.value or nb.value:
+        _check(None, fn(h, rec.ctypes.data if nr.value else None, nr.value, C.byref(nr), raw.ctypes.data, nb.value, C.byref(nb), C.byref(no), C.byref(ns)))
+    return rec[:nr.value], raw[:nb.value].tobytes(), no.value, ns.value
+
+
+def cigars_pack_host(words, part_ops: int = 0, seg_ops: int = 0) -> bytes:
+    """cl_cigars_pack_host: the coded segments of the operation words, by the host twin; ValueError names the first word that is no operation"""
+    lib = N.load()
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    nb, bad = C.c_uint64(0), C.c_uint64(0)
+    st = lib.cl_cigars_pack_host(w.ctypes.data if w.size else None, w.size, part_ops, seg_ops, None, 0, C.byref(nb), C.byref(bad))
+    if st == N.CL_E_INVALID:
+        raise ValueError("cl_cigars_pack_host: word %d is no operation" % bad.value if bad.value != 2 ** 64 - 1 else "cl_cigars_pack_host: a knob out of range")
+    out = np.zeros(max(nb.value, 1), np.uint8)
+    st = lib.cl_cigars_pack_host(w.ctypes.data if w.size else None, w.size, part_ops, seg_ops, out.ctypes.data, nb.value, C.byref(nb), C.byref(bad))
+    assert st == N.CL_OK, st
+    return out[:nb.value].tobytes()
+
+
+def cigars_unpack_host(data: bytes) -> np.ndarray:
+    """cl_cigars_unpack_host: the operation words of coded segments; ValueError with the reason (cl_cigars_check_host) when they are refused"""
+    lib = N.load()
+    raw = np.frombuffer(data, np.uint8)
+    no = C.c_uint64(0)
+    st = lib.cl_cigars_unpack_host(raw.ctypes.data if raw.size else None, raw.size, None, 0, C.byref(no))
+    if st == N.CL_E_INVALID:
+        raise ValueError(lib.cl_cigars_refusal(lib.cl_cigars_check_host(raw.ctypes.data if raw.size else None, raw.size)).decode())
+    out = np.zeros(max(no.value, 1), np.uint32)
+    st = lib.cl_cigars_unpack_host(raw.ctypes.data if raw.size else None, raw.size, out.ctypes.data, no.value, C.byref(no))
+    assert st == N.CL_OK, st
+    return out[:no.value].copy()
+
+
 class Compressor(_Obj):
     """cl_compressor: pass 1 / reference listing / pass 2 over the chunks of an input (csrc/stream.hip)."""
     _free = "cl_compressor_free"
+
+    def cigars_coded(self):
+        """cl_compressor_cigars_coded: the record counts and the coded segments of the CIGARs (Context.set_cigars_coded)."""
+        return _cigar_coded(self.ctx.lib.cl_compressor_cigars_coded, self.h)
 
     def cigars(self):
         """cl_compressor_cigars: the CIGARs of the records of mappings() (Context.set_cigars), in their order."""

@@ -665,6 +665,33 @@ const char* cl_cigars_error(uint32_t code);
 cl_status cl_ctx_set_cigars(cl_ctx* ctx, int on);
 cl_status cl_ctx_cigars(const cl_ctx* ctx, uint32_t* h_rec_ops, uint64_t rec_cap, uint64_t* n_rec, uint32_t* h_ops, uint64_t ops_cap, uint64_t* n_ops);
 
+/* ---- coded CIGARs (no counterpart in the reference) — the operations as the bytes of a static-model interval coder ----- */
+/* An operation word len << 4 | op gives two symbols: the op symbol o (I 0, D 1, = 2, X 3), coded in the context of the o of the word
+ * before it in flat order (context 4 at a part's first word), and the length symbol len - 1 for len <= 255, else 255 (escape: len follows
+ * as a raw u32 in the segment's escape list), coded in the context of its own o.  The words of a call are cut into segments of seg_ops
+ * (0: the default and maximum, 2^20), a segment into parts of part_ops (0: the default, 4096; at most 2^16); a part is one restart of the
+ * interval coder.  The model is static per segment: the 20 + 1024 counts of its symbols are the frequencies.  Segment bytes, little-endian:
+ * u32 n_ops, u32 part_ops, u32 n_escapes, u32 table_bytes; the part sizes as u32; the 1044 counts as LEB128; the escapes; the parts.
+ * cl_cigars_pack: n_ops words in DEVICE memory (any sequence of words with an op of I D = X and len >= 1: record boundaries play no role)
+ * -> the bytes of their segments in h_out (*n_bytes; 0 words give 0 bytes).  Histogram, model and interval coder run on the device; the
+ * host copies the coded bytes.  cap too small (or h_out null): CL_E_CAPACITY with the need and nothing written.  Another word is
+ * CL_E_INVALID, the text naming the first such index; a knob out of range too.  cl_cigars_pack_host: the same bytes from one host thread
+ * (*bad_index, optional: the first word that is no operation, else ~0).  cl_cigars_unpack_host: the words back (*n_ops; CL_E_CAPACITY with
+ * the need); bytes that are not whole segments of this format, in any way, are CL_E_INVALID and nothing outside them is read —
+ * cl_cigars_check_host says why (0: they decode), cl_cigars_refusal gives the text. */
+cl_status cl_cigars_pack(cl_ctx* ctx, const uint32_t* d_ops, uint64_t n_ops, uint32_t part_ops, uint32_t seg_ops, uint8_t* h_out, uint64_t cap, uint64_t* n_bytes);
+cl_status cl_cigars_pack_host(const uint32_t* h_ops, uint64_t n_ops, uint32_t part_ops, uint32_t seg_ops, uint8_t* h_out, uint64_t cap, uint64_t* n_bytes, uint64_t* bad_index);
+cl_status cl_cigars_unpack_host(const uint8_t* bytes, uint64_t n, uint32_t* h_ops, uint64_t cap, uint64_t* n_ops);
+uint32_t cl_cigars_check_host(const uint8_t* bytes, uint64_t n);
+const char* cl_cigars_refusal(uint32_t code);
+/* Opt-in on top of cl_ctx_set_cigars (CL_E_INVALID without it; switching the CIGARs off switches this off): a batch's operations are coded
+ * right after they are made and only the coded bytes come to the host.  cl_ctx_cigars decodes them there; cl_ctx_cigars_coded gives the
+ * record counts (as cl_ctx_cigars) and the segments of all batches one behind the other, in the batches' order, with their operations and
+ * segments counted (CL_E_CAPACITY with the needs and nothing written; CL_E_INVALID when a batch was kept raw).  Segment bytes depend on how
+ * the input was batched; the decoded operations do not. */
+cl_status cl_ctx_set_cigars_coded(cl_ctx* ctx, int on);
+cl_status cl_ctx_cigars_coded(const cl_ctx* ctx, uint32_t* h_rec_ops, uint64_t rec_cap, uint64_t* n_rec, uint8_t* h_bytes, uint64_t cap, uint64_t* n_bytes, uint64_t* n_ops, uint64_t* n_segments);
+
 /* ---- pileup (no counterpart in the reference) — what a reference-genome run aligned, per genome position ------------- */
 /* The second half of what a -G run aligns: which genome position every read base was aligned to, and what the read said there.  The
  * geometry is that of cl_mappings_lift; the table has n_pos = sum of seq_len[s] positions, sequence s from the sum of the lengths before
@@ -912,6 +939,8 @@ cl_status cl_compressor_genome_geometry(cl_compressor* c, const uint64_t* h_seq_
 cl_status cl_compressor_mappings(const cl_compressor* c, cl_overlap* h_out, uint64_t cap, uint64_t* n_out);
 /* cl_ctx_cigars of the compressor's context (cl_ctx_set_cigars): after the last cl_compressor_encode, of every chunk */
 cl_status cl_compressor_cigars(const cl_compressor* c, uint32_t* h_rec_ops, uint64_t rec_cap, uint64_t* n_rec, uint32_t* h_ops, uint64_t ops_cap, uint64_t* n_ops);
+/* cl_ctx_cigars_coded of the compressor's context (cl_ctx_set_cigars_coded) */
+cl_status cl_compressor_cigars_coded(const cl_compressor* c, uint32_t* h_rec_ops, uint64_t rec_cap, uint64_t* n_rec, uint8_t* h_bytes, uint64_t cap, uint64_t* n_bytes, uint64_t* n_ops, uint64_t* n_segments);
 /* The compressor's table (cl_ctx_set_pileup), finished, after the last cl_compressor_encode: *out belongs to the compressor and goes
  * with it.  CL_E_INVALID: the flag was off when the references were finished, or chunks are still to be coded. */
 cl_status cl_compressor_pileup(cl_compressor* c, cl_pileup** out);
