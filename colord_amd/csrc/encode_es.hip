@@ -10,8 +10,9 @@
 //   side3:  class 7, k_giant_stage / _level / _leaves / _finish: many waves per gap (align_giant.hpp)
 //   main:   class 6, k_align_wave: a wave per gap on a bump pool in HBM, in rounds of growing pools (the host reads each round's redo list);
 //           then the redo lists of class 5 and of class 7, read back in that order and run through the same rounds
-//   main stream, when classes 1-4 are through too: k_gap_stats[_long] (estimator statistics or the static entropy decision) ->
-//                k_gap_sums[_long] -> k_spawn_mark -> scans -> k_spawn_fill.
+//   main stream, when classes 1-4 are through too: k_gap_tail (a row of 16 lanes per gap: trivial scripts, estimator statistics or the static
+//                entropy decision, run summary; gap_tail.hpp) -> k_gap_stats_long -> k_gap_sums_long (a wave per gap, the few scripts beyond
+//                the row limit) -> k_spawn_mark -> scans -> k_spawn_fill.
 // Then k_estimator (one wave per reader pack) and k_emit_count_wave / k_emit_write_wave (one wave per read; emit_wave.hpp), k_emit_plain.
 #include "objects.hpp"
 #include "encode_core.hpp"
@@ -19,6 +20,7 @@
 #include "align_rows.hpp"
 #include "align_giant.hpp"
 #include "emit_wave.hpp"
+#include "gap_tail.hpp"
 #include <algorithm>
 #include <chrono>
 #include <climits>
@@ -764,25 +766,34 @@ __global__ __launch_bounds__(64) void k_align_quad_rows(const uint32_t* __restri
 // (no lane-per-gap kernel: align_large (align_dev.hpp) and align_large_gap (encode_core.hpp) stay as the reference that
 // tests/tools/encode_host.hip compiles for the host and the device aligners are compared with)
 
-// short gaps (the estimator decides them later): one lane per gap; long gaps are listed for k_gap_stats_long
-__global__ void k_gap_stats(LevelV L, ArenaV A, EncCfg cfg, const uint32_t* __restrict__ pend_idx, uint32_t* __restrict__ spawn_flag, uint32_t* __restrict__ long_list)
+// the tail of a level (gap_tail.hpp): trivial scripts, estimator statistics or the static entropy decision, the spawn flag and the run
+// summary of every gap in one pass over its script.  One 16-lane ROW per gap, four gaps per wave, taken through the list sorted by class
+// and size, so that the rows of a wave hold scripts of similar length.  A script beyond row_limit symbols is listed for the two
+// whole-wave kernels below (the order of that list decides nothing)
+__global__ __launch_bounds__(256) void k_gap_tail(LevelV L, ArenaV A, EncCfg cfg, const uint32_t* __restrict__ ids, const uint32_t* __restrict__ pend_idx, GapSum* __restrict__ sums,
+                                                  uint32_t* __restrict__ spawn_flag, uint32_t row_limit, uint32_t* __restrict__ over_ids, unsigned int* __restrict__ n_over)
 {
-	const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
-	if (gi >= L.n_gaps) return;
-	if (L.gaps[gi].ne >= cfg.min_part_alt) { long_list[gi - pend_idx[gi]] = gi; return; }      // pend_idx = number of short gaps before gi
-	spawn_flag[gi] = gap_finish(L, gi, A, cfg, pend_idx[gi]) ? 1u : 0u;
+	const uint64_t ri = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
+	if (ri >= L.n_gaps) return;
+	const uint32_t gi = ids[ri];
+	const GapRec g = L.gaps[gi];
+	const uint32_t k = g.kind == GK_TRIVIAL && g.nr == 0 ? g.ne : g.es_len;       // a trivial gap's script is made here
+	if (k > row_limit) { if ((threadIdx.x & 15) == 0) over_ids[atomicAdd(n_over, 1u)] = gi; return; }
+	gap_tail_group<16, true>(L, A, cfg, gi, g, pend_idx[gi], sums, spawn_flag);      // pend_idx = number of short gaps before gi
 }
-// run summaries of the scripts for the count pass of the tuple emission: one lane per gap
-__global__ void k_gap_sums(LevelV L, GapSum* __restrict__ sums, uint32_t* __restrict__ long_ids, unsigned int* __restrict__ n_long)
+// ... the listed gaps by a wave each: statistics / decision (their run summaries: k_gap_sums_long, which reads the script lengths set here)
+__global__ __launch_bounds__(256) void k_gap_stats_long(LevelV L, ArenaV A, EncCfg cfg, const uint32_t* __restrict__ pend_idx, const uint32_t* __restrict__ over_ids,
+                                                        const unsigned int* __restrict__ n_over, uint32_t* __restrict__ spawn_flag)
 {
-	const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
-	if (gi >= L.n_gaps) return;
-	const uint32_t k = L.gaps[gi].es_len;
-	if (k && k <= SUM_LIMIT) sums[gi] = gap_summary(L.es + L.gaps[gi].es_off, k);
-	else if (k) long_ids[atomicAdd(n_long, 1u)] = gi;                          // (k_gap_sums_long)
+	const uint32_t n = *n_over, n_waves = gridDim.x * 4;
+	for (uint32_t idx = blockIdx.x * 4 + (threadIdx.x >> 6); idx < n; idx += n_waves)
+	{
+		const uint32_t gi = over_ids[idx];
+		gap_tail_group<64, false>(L, A, cfg, gi, L.gaps[gi], pend_idx[gi], nullptr, spawn_flag);
+	}
 }
-// ... and of the long scripts by a wave each (the wave-per-read emission works from summaries alone; a lane would take a
-// millisecond for the 10^5 symbols of a long flank and hold its launch that long)
+// ... and their run summaries (the wave-per-read emission works from summaries alone; a lane would take a millisecond for the 10^5
+// symbols of a long flank and hold its launch that long)
 __global__ __launch_bounds__(256) void k_gap_sums_long(LevelV L, GapSum* __restrict__ sums, const uint32_t* __restrict__ long_ids, const unsigned int* __restrict__ n_long)
 {
 	const uint32_t n = *n_long, n_waves = gridDim.x * 4;
@@ -792,91 +803,6 @@ __global__ __launch_bounds__(256) void k_gap_sums_long(LevelV L, GapSum* __restr
 		const RunEl a = run_of_script_wave(L.es + L.gaps[gi].es_off, L.gaps[gi].es_len);
 		if ((threadIdx.x & 63) == 0) sums[gi] = GapSum{ a.hl, a.tl, a.mb, a.mt, a.hs | (a.ts << 8) | (a.single ? 1u << 16 : 0u) };
 	}
-}
-// long gaps: the static entropy test (EncodeWithEditScript, encoder.cpp:1315-1327; CEntropy, utils.h:706-752) by one wave
-__global__ __launch_bounds__(256) void k_gap_stats_long(LevelV L, ArenaV A, EncCfg cfg, const uint32_t* __restrict__ long_list, uint32_t n_long, uint32_t* __restrict__ spawn_flag)
-{
-	const uint32_t wi = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-	if (wi >= n_long) return;
-	const uint32_t gi = long_list[wi];
-	GapRec g = L.gaps[gi];
-	char* es = L.es + g.es_off;
-	const uint64_t ewb = A.word_off[g.read];
-	if (g.kind == GK_TRIVIAL)
-	{	// get_edit_dist_on_seq_empty (edit_script.h:250-267)
-		if (g.nr == 0) { for (uint32_t i = lane; i < g.ne; i += 64) es[i] = base_letter(arena_base_at(A, ewb, g.enc_start + i)); g.es_len = g.ne; }
-		else g.d_before = g.nr;
-		__builtin_amdgcn_s_waitcnt(0);
-		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-	}
-	// leading deletions (GetEditScriptEntropyInput, encoder.cpp:1299-1311)
-	uint32_t nd = 0;
-	for (uint32_t i0 = 0; i0 < g.es_len; i0 += 64)
-	{
-		const uint32_t i = i0 + lane;
-		const uint64_t notd = __ballot(i < g.es_len && es[i] != 'D');
-		if (notd) { nd = i0 + (uint32_t)__builtin_ctzll(notd); break; }
-		nd = i0 + 64 < g.es_len ? i0 + 64 : g.es_len;
-	}
-	uint32_t h[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, hd[4] = { 0, 0, 0, 0 };
-	// the script eight symbols per lane and load, the read's bases a packed word (32 bases) per lane and load, counted by popcounts: a byte
-	// and a base per lane were es_len / 64 + ne / 64 load latencies in a row for every gap
-	for (uint32_t i = lane * 8; i < g.es_len; i += 512)
-	{
-		uint64_t w = 0; uint32_t nb = 8;
-		if (i + 8 <= g.es_len) __builtin_memcpy(&w, es + i, 8);
-		else { nb = g.es_len - i; for (uint32_t y = 0; y < nb; ++y) w |= (uint64_t)(uint8_t)es[i + y] << (8 * y); }
-		for (uint32_t y = 0; y < nb; ++y)
-		{
-			const uint32_t c = es_class((char)((w >> (8 * y)) & 0xffu));
-#pragma unroll
-			for (int k = 0; k < 9; ++k) h[k] += c == (uint32_t)k;
-		}
-	}
-	if (g.ne)
-	{
-		const uint32_t s = g.enc_start, last = g.enc_start + g.ne - 1, w0 = s >> 5, w1 = last >> 5;
-		for (uint32_t wi2 = w0 + lane; wi2 <= w1; wi2 += 64)
-		{
-			const uint64_t w = A.packed[ewb + wi2];
-			const uint32_t ja = wi2 == w0 ? (s & 31) : 0u, jb = wi2 == w1 ? (last & 31) : 31u;    // fields (bases) ja .. jb of the word count; base j sits at bits 63 - 2 j, 62 - 2 j
-			const uint64_t from = ja == 0 ? ~0ull : ((1ull << (64 - 2 * ja)) - 1), upto = ~((1ull << (62 - 2 * jb)) - 1);
-			const uint64_t v = from & upto & 0x5555555555555555ull, lo = w & 0x5555555555555555ull, hi = (w >> 1) & 0x5555555555555555ull;
-			const uint32_t c3 = (uint32_t)__popcll(lo & hi & v), c2 = (uint32_t)__popcll(hi & ~lo & v), c1 = (uint32_t)__popcll(lo & ~hi & v);
-			hd[3] += c3; hd[2] += c2; hd[1] += c1; hd[0] += (uint32_t)__popcll(v) - c1 - c2 - c3;
-		}
-	}
-#pragma unroll
-	for (int k = 0; k < 9; ++k) for (int o = 32; o; o >>= 1) h[k] += __shfl_xor(h[k], o);
-#pragma unroll
-	for (int k = 0; k < 4; ++k) for (int o = 32; o; o >>= 1) hd[k] += __shfl_xor(hd[k], o);
-	uint32_t n = g.es_len, extra = g.d_before;
-	if (nd + g.d_before >= 10) { h[2] -= nd; n -= nd; extra = 0; }                 // the script is scored without its leading deletions
-	h[2] += extra;
-	// the two entropies (entropy_hist, encode_core.hpp): their thirteen p log2 p terms one per lane in ONE evaluation of the logarithm (lanes
-	// 0 .. 8 the script's classes, 16 .. 19 the bases) instead of thirteen in a row on every lane; the sums run over the terms in the
-	// sequential order, so the doubles are the sequential ones
-	double sum_h = 0, sum_d = 0;
-#pragma unroll
-	for (int i = 0; i < 9; ++i) sum_h += h[i];
-#pragma unroll
-	for (int i = 0; i < 4; ++i) sum_d += hd[i];
-	const double rec_h = 1.0 / sum_h, rec_d = 1.0 / sum_d;
-	uint32_t mine = 0;
-#pragma unroll
-	for (int i = 0; i < 9; ++i) if (lane == (uint32_t)i) mine = h[i];
-#pragma unroll
-	for (int i = 0; i < 4; ++i) if (lane == 16u + (uint32_t)i) mine = hd[i];
-	double term = 0;
-	if (mine) { const double p = (double)mine * (lane < 16 ? rec_h : rec_d); term = glibc_log2::log2(p) * p; }
-	double e_h = 0, e_d = 0;
-#pragma unroll
-	for (int i = 0; i < 9; ++i) { const double t = __shfl(term, i, 64); if (h[i]) e_h += t; }
-#pragma unroll
-	for (int i = 0; i < 4; ++i) { const double t = __shfl(term, 16 + i, 64); if (hd[i]) e_d += t; }
-	const bool accept = -e_h * (double)(n + extra) * cfg.cost_mult < -e_d * (double)g.ne;
-	g.state = accept ? GS_ES : GS_REJECTED;
-	if (lane == 0) { L.gaps[gi] = g; spawn_flag[gi] = accept ? 0u : 1u; }
 }
 // rejected long gaps: continue in a child frame when an alternative candidate still has anchors there, else literal
 __global__ void k_spawn_mark(LevelV L, const uint32_t* __restrict__ data, EncCfg cfg, uint32_t* __restrict__ flag, uint32_t* __restrict__ ncand)
@@ -1073,13 +999,15 @@ namespace {
 struct EncKnobs {
 	uint32_t small_per_cu, quad_waves;   // tuning: blocks of k_align_small per CU (15 - 25 KB of LDS each), waves of k_align_quad_rows at most (18.5 KB each)
 	uint32_t wave_debug_stage;           // handed to k_align_wave
+	uint32_t tail_row_limit;             // k_gap_tail: scripts up to this many symbols are taken by a row of 16 lanes, longer ones by a wave
 	bool no_team_align;                  // the giant gaps go to the wave kernel (tools/giant_check.py's comparison)
 	bool gap_debug, gap_shapes, quad_profile, wave_profile, wave_heartbeat;   // the diagnostics of encode_diag.hpp
 	static EncKnobs read()
 	{
 		auto num = [](const char* name, int dflt, int least) { const char* e = getenv(name); return (uint32_t)(e ? std::max(least, atoi(e)) : dflt); };
 		auto on = [](const char* name) { return getenv(name) != nullptr; };
-		return EncKnobs{ num("COLORD_HIP_SMALL_PER_CU", 4, 1), num("COLORD_HIP_QUAD_WAVES", 2048, 64), num("COLORD_HIP_WAVE_DEBUG_STAGE", 0, INT_MIN), on("COLORD_HIP_NO_TEAM_ALIGN"),
+		return EncKnobs{ num("COLORD_HIP_SMALL_PER_CU", 4, 1), num("COLORD_HIP_QUAD_WAVES", 2048, 64), num("COLORD_HIP_WAVE_DEBUG_STAGE", 0, INT_MIN),
+			num("COLORD_HIP_TAIL_ROW_LIMIT", (int)SUM_LIMIT, 0), on("COLORD_HIP_NO_TEAM_ALIGN"),
 			on("COLORD_HIP_GAP_DEBUG"), on("COLORD_HIP_GAP_SHAPES"), on("COLORD_HIP_QUAD_PROFILE"), on("COLORD_HIP_WAVE_PROFILE"), on("COLORD_HIP_WAVE_HEARTBEAT") };
 	}
 };
@@ -1100,8 +1028,8 @@ struct LevelWork {
 	double bytes(uint32_t cls) const { return 1.25 * (double)h_cb[cls]; }   // 2-bit symbols in, a script byte per symbol out
 	double cells(uint32_t cls) const { return (double)h_cb[N_CLASSES + cls]; }
 };
-// ... and those of its decisions and children (declared after the aligners' objects): spawn flag (scanned), its candidates, the two lists of long gaps, candidate offset
-struct SpawnWork { DevBuf<uint32_t> sflag, sncand, long_list, sum_long; DevBuf<uint64_t> cbase; };
+// ... and those of its decisions and children (declared after the aligners' objects): spawn flag (scanned), its candidates, the list of the gaps whose scripts are beyond the row limit, candidate offset
+struct SpawnWork { DevBuf<uint32_t> sflag, sncand, over_list; DevBuf<uint64_t> cbase; };
 
 // Joins a side stream on every way out of its scope.  As the LAST member of an object it is destroyed FIRST: the object's buffers
 // outlive the kernels of the stream that use them, also when a step returns early with an error.
@@ -1355,15 +1283,17 @@ cl_status level_decisions(const EncCall& E, LevelBufs& L, const LevelWork& W, Sp
 {
 	cl_ctx* ctx = E.ctx; const uint64_t ng = W.ng;
 	DEV_ALLOC(ctx, S.sflag, ng + 1); DEV_ALLOC(ctx, S.sncand, ng + 1);
-	const uint32_t n_long = (uint32_t)(ng - W.n_pend);
-	DEV_ALLOC(ctx, S.long_list, (uint64_t)n_long + 1);
-	LAUNCH(ctx, k_gap_stats, grid_for(ng, 64), 64, W.V, E.A, E.cfg, (const uint32_t*)W.pflag.p, S.sflag.p, S.long_list.p);
-	if (n_long) LAUNCH(ctx, k_gap_stats_long, grid_for((uint64_t)n_long * 64, 256), 256, W.V, E.A, E.cfg, (const uint32_t*)S.long_list.p, n_long, S.sflag.p);
 	DEV_ALLOC(ctx, L.sums, ng + 1);
-	DEV_ALLOC(ctx, S.sum_long, ng + 2);                                        // ids of the gaps with long scripts, their number in the last word
-	HIP_TRY(ctx, hipMemsetAsync(S.sum_long.p + ng + 1, 0, 4, E.st));
-	LAUNCH(ctx, k_gap_sums, grid_for(ng, 64), 64, W.V, L.sums.p, S.sum_long.p, (unsigned int*)(S.sum_long.p + ng + 1));
-	LAUNCH(ctx, k_gap_sums_long, 1024, 256, W.V, L.sums.p, (const uint32_t*)S.sum_long.p, (const unsigned int*)(S.sum_long.p + ng + 1));
+	DEV_ALLOC(ctx, S.over_list, ng + 2);                                       // ids of the gaps left to the whole-wave kernels, their number in the last word
+	unsigned int* n_over = (unsigned int*)(S.over_list.p + ng + 1);
+	HIP_TRY(ctx, hipMemsetAsync(n_over, 0, 4, E.st));
+	// algorithmic bytes: the scripts (about half their capacity of reference + read symbols) and the read's 2-bit bases under them, a gap
+	// record read and written, id, pending index, spawn flag and summary per gap, a pending record per short gap
+	const double tail_bytes = 0.625 * (double)W.es_total + (double)ng * (2 * sizeof(GapRec) + sizeof(GapSum) + 12) + (double)W.n_pend * sizeof(PendRec);
+	LAUNCHB(ctx, tail_bytes, k_gap_tail, grid_for(ng * 16, 256), 256, W.V, E.A, E.cfg, (const uint32_t*)W.ids.p, (const uint32_t*)W.pflag.p, L.sums.p, S.sflag.p,
+		E.knobs.tail_row_limit, S.over_list.p, n_over);
+	LAUNCH(ctx, k_gap_stats_long, 1024, 256, W.V, E.A, E.cfg, (const uint32_t*)W.pflag.p, (const uint32_t*)S.over_list.p, (const unsigned int*)n_over, S.sflag.p);
+	LAUNCH(ctx, k_gap_sums_long, 1024, 256, W.V, L.sums.p, (const uint32_t*)S.over_list.p, (const unsigned int*)n_over);
 	LAUNCH(ctx, k_spawn_mark, grid_for(ng, 64), 64, W.V, E.AV.data, E.cfg, S.sflag.p, S.sncand.p);
 	HIP_TRY(ctx, hipGetLastError());
 	return CL_OK;
